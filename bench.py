@@ -1,6 +1,13 @@
 """Headline benchmark: decoded frames/s, P(128,64)+CRC-24 SCL L=8 at Eb/N0 = 5 dB (BASELINE.json).
 
     python bench.py [--gpus N --steps K --warmup W --frames B --list L --ebno 5.0]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, ms_per_step,
+the roofline of the timed launches and the FER/BER counters of the timed steps.  --dump-outputs
+DIR also writes what the last timed step returned to its caller (DIR/<name>.npy, dump_outputs).
+Everything that takes runs of its own -- parity, cpu_baseline, extra_configs below -- is behind
+--full; without it those keys are null.
 
 One step = one pass of the hot path over one batch of B frames per GPU that is already
 resident in HBM: SCL decode (fp64, bit-exact to the reference) + CRC selection + FER/BER
@@ -8,7 +15,7 @@ counting, i.e. run_fer_sweep.py:79-109 without the TX chain.  The batches are ge
 on the device before the timed region by the Philox TX kernel (payload -> CRC-24 ->
 polar encode -> BPSK -> AWGN -> LLR), distinct frames per step and per rank.
 
-The line also carries
+The line also carries (parity and extra_configs with --full only)
   parity        the step-0 batch decoded again after the timed region and compared frame by
                 frame (best bits, CRC flag, best index) with the oracle's outputs for the
                 frames the CPU baseline decoded (oracle/: C restatement of decode_scl);
@@ -73,8 +80,13 @@ def parse():
     ap.add_argument("--list", type=int, default=8)
     ap.add_argument("--ebno", type=float, default=5.0)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="budget for the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the oracle legs (cpu_baseline, step-0 parity) and, for the "
+                         "default workload, extra_configs; --no-cpu-baseline and --extra none switch either off")
+    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="budget for the CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no oracle legs")
     ap.add_argument("--retries", type=int, default=0,
                     help="DL-SCL flip retries per CRC-failing frame (BASELINE config 4: --list 4 --retries 8)")
     ap.add_argument("--beta", type=str, default="auto",
@@ -87,7 +99,7 @@ def parse():
                     help="schedule knobs of the bench's decode handle, k=v[,k=v] (pscl_set_tuning: dl_screen, "
                          "dl_chunks, dl_split, side_priority, post_grid, retry_wpg, dl_lane); A/B tools only")
     ap.add_argument("--extra", choices=["auto", "none"], default="auto",
-                    help="auto: also time BASELINE configs 2, 4, 5 (extra_configs) after the headline")
+                    help="with --full, auto: also time BASELINE configs 2, 3, 4, 5 (extra_configs) after the headline")
     ap.add_argument("--extra-steps", type=int, default=20)
     ap.add_argument("--extra-parity", type=int, default=50_000, help="oracle parity frames per extra config")
     return ap.parse_args()
@@ -372,10 +384,11 @@ TUNE: dict = {}  # --tune
 
 
 def run_workload(ctx: Ctx, *, L: int, E: int, retries: int, beta, B: int, steps: int, warmup: int, ebno: float,
-                 seed: int, keep_buffers: bool = False):
+                 seed: int, keep_buffers: bool = False, step0: bool = True, keep_last: bool = False):
     """Generate the batches on the device, run W untimed + K timed steps (barrier and
-    synchronize on both sides, max over ranks), then decode the step-0 batch once more
-    (untimed) for the parity check.  Returns the measurements."""
+    synchronize on both sides, max over ranks), then (step0) decode the step-0 batch once more
+    (untimed) for the parity check.  keep_last: the last timed step's output buffers come back
+    on the host ("last").  Returns the measurements."""
     torch, dev = ctx.torch, ctx.dev
     from polar_code_amd import _native
     from polar_code_amd.polar.polar import construct_info_set
@@ -452,22 +465,57 @@ def run_workload(ctx: Ctx, *, L: int, E: int, retries: int, beta, B: int, steps:
     elapsed = ctx.max_over_ranks(elapsed)
     c = ctx.sum_over_ranks(counters)
     cdl = ctx.sum_over_ranks(counters_dl)
-    # untimed: the step-0 batch once more, outputs kept for the parity check
-    step(0, count=False)
-    best, flags = best_b[(calls[0] - 1) % depth], flags_b[(calls[0] - 1) % depth]
-    dec.sync()
-    torch.cuda.synchronize(dev)
     res = {"N": N, "K": K, "W": W, "L": L, "E": E, "B": B, "n_in": n_in, "info": info, "retries": retries,
            "elapsed": elapsed, "launches": launches, "kern_ms": kern_ms, "side_launches": side_launches,
            "side_ms": side_ms, "c": c, "cdl": cdl, "kp": kp,
-           "rate": rate, "build_hash": _native.build_hash(), "pipelined": pipelined,
-           "best0": best.cpu().numpy().view(np.uint64), "flags0": flags.cpu().numpy()}
+           "rate": rate, "build_hash": _native.build_hash(), "pipelined": pipelined}
+    if keep_last and steps > 0:  # this rank's last timed step (complete: joined and synchronized above)
+        last = (calls[0] - 1) % depth
+        res["last"] = {"best": best_b[last].cpu().numpy().view(np.uint64), "flags": flags_b[last].cpu().numpy()}
+    if step0:
+        # untimed: the step-0 batch once more, outputs kept for the parity check
+        step(0, count=False)
+        best, flags = best_b[(calls[0] - 1) % depth], flags_b[(calls[0] - 1) % depth]
+        dec.sync()
+        torch.cuda.synchronize(dev)
+        res["best0"], res["flags0"] = best.cpu().numpy().view(np.uint64), flags.cpu().numpy()
+        del best, flags
     if keep_buffers:
         res["llr0"] = llr[0]
-    del llr, msg, best, flags, best_b, flags_b
+    del llr, msg, best_b, flags_b
     dec.close()
     torch.cuda.empty_cache()
     return res
+
+
+DUMP_MAX_FRAMES = 131072  # x (K <= 88 bits + 3 columns) x 4 bytes: under 64 MB for every workload
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, r: dict) -> None:
+    """--dump-outputs: what the last timed step handed back to its caller, as float .npy files.
+    Rank 0's batch; of a batch larger than DUMP_MAX_FRAMES a fixed seeded sample of frames (their
+    indices in frame_index.npy).  The inputs are a function of the arguments alone (Philox frames
+    keyed by seed and global frame index) and the decode is exact, so two builds given the same
+    arguments must write the same files."""
+    from polar_code_amd.dlscl.flip import words_to_bits
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    best, flags = r["last"]["best"], r["last"]["flags"]
+    B = flags.shape[0]
+    idx = np.arange(B)
+    if B > DUMP_MAX_FRAMES:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=DUMP_MAX_FRAMES, replace=False))
+    f = flags[idx]
+    np.save(d / "frame_index.npy", idx.astype(np.float64))
+    np.save(d / "best_bits.npy", words_to_bits(best[idx], r["K"]).astype(np.float32))  # [n, K] 0/1
+    np.save(d / "crc_pass.npy", ((f & 0x80) != 0).astype(np.float32))
+    np.save(d / "best_idx.npy", (f & 0x3F).astype(np.float32))
+    # the device counters the steps accumulate (all timed steps, summed over ranks; < 2^53)
+    np.save(d / "counters.npy", np.asarray(r["c"], dtype=np.float64))
+    if r["retries"] > 0:
+        np.save(d / "counters_dl.npy", np.asarray(r["cdl"], dtype=np.float64))
 
 
 def extra_configs(args, ctx: Ctx, orc: Oracle | None):
@@ -770,15 +818,20 @@ def main():
     if args.retries > 0 and args.beta != "none":
         bp = ROOT / "tests" / "golden" / f"beta_M{L}.npy" if args.beta == "auto" else Path(args.beta)
         beta = np.load(bp) if bp.exists() else None
+    oracle_legs = args.full and rank == 0 and not args.no_cpu_baseline
     r = run_workload(ctx, L=L, E=E, retries=args.retries, beta=beta, B=B, steps=args.steps, warmup=args.warmup,
-                     ebno=args.ebno, seed=args.seed, keep_buffers=(rank == 0))
+                     ebno=args.ebno, seed=args.seed, keep_buffers=oracle_legs, step0=oracle_legs,
+                     keep_last=bool(args.dump_outputs) and rank == 0)
     heartbeat("headline")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r)
+        r.pop("last", None)
     N, K, W, n_in, info, kp = r["N"], r["K"], r["W"], r["n_in"], r["info"], r["kp"]
     c, cdl, elapsed = r["c"], r["cdl"], r["elapsed"]
     frames_total = B * args.steps * world
 
     cpu = par = None
-    orc = Oracle() if (rank == 0 and not args.no_cpu_baseline) else None
+    orc = Oracle() if oracle_legs else None
     host = None
     if orc is not None:
         host = r["llr0"][: min(B, 1_000_000)].cpu().numpy()
@@ -787,7 +840,7 @@ def main():
     r.pop("llr0", None)
     torch.cuda.empty_cache()
     extra = None
-    if args.extra == "auto" and not E and args.retries == 0 and L == 8:
+    if args.full and args.extra == "auto" and not E and args.retries == 0 and L == 8:
         # (the sweep first: the extra configs' oracle parity checks run the oracle on every CPU of
         # the affinity mask, after which the host-timed sweep measured ~4 % slower)
         sweep = config3_sweep(args, ctx)

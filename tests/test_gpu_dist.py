@@ -145,7 +145,7 @@ def test_world1_rccl_group_equals_no_group(tmp_path):
 
 @pytest.mark.timeout(900)
 def test_bench_gpus2_default_extras_equal_world1():
-    """The driver's multi-GPU command with its default extras (`bench.py --gpus 2`, no --extra
+    """The multi-GPU command with every leg of the full run (`bench.py --gpus 2 --full`, no --extra
     none): every extra config and the config-3 sweep run under a 2-rank process group (rank 0's
     oracle parity sample while the other rank waits at a collective included), rank 0's single
     line carries extra_configs and config3_sweep_L8, and every counter equals the world-1 run
@@ -156,7 +156,7 @@ def test_bench_gpus2_default_extras_equal_world1():
     env.update(PSCL_SHARE_GPU="1", PSCL_DIST_BACKEND="gloo")
     line = {}
     for gpus, frames in ((1, 2 * B), (2, B)):
-        cmd = [sys.executable, "bench.py", "--gpus", str(gpus), "--frames", str(frames), "--steps", str(S),
+        cmd = [sys.executable, "bench.py", "--gpus", str(gpus), "--full", "--frames", str(frames), "--steps", str(S),
                "--warmup", "1", "--extra-steps", str(E), "--extra-parity", "4000", "--cpu-seconds", "1"]
         res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]

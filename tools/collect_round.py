@@ -4,6 +4,7 @@ gpurun_out/ into profiles/ and record its PMC summary in profiles/pmc_traffic.js
     python tools/collect_round.py <tag>
 """
 import json
+import os
 import shutil
 import subprocess
 import sys
@@ -31,7 +32,8 @@ for src, dst in copies.items():
     if src.exists():
         shutil.copy(src, dst)
         print("copied", dst.name)
-for src, dst in ((G / f"{tag}_bench.log", P / f"{tag}_bench_default.json"),
+BENCH_LOG = Path(os.environ.get("OUT_DIR") or ROOT / "_out") / f"{tag}_bench.log"  # (gpu_round.sh: bench.py --full)
+for src, dst in ((BENCH_LOG, P / f"{tag}_bench_default.json"),
                  (G / f"prof_{tag}" / "bench.log", P / f"{tag}_bench_under_rocprof.json"),
                  (G / f"prof_dl_{tag}" / "bench.log", P / f"{tag}_bench_dl_under_rocprof.json")):
     if src.exists() and bench_line(src):

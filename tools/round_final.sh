@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-final GPU pass on the frozen build: full GPU suite, smoke, default bench line,
+# Round-final GPU pass on the frozen build: full GPU suite, smoke, full bench line,
 # rocprofv3 kernel stats + PMC passes of the headline, long codes, config-3 sweep, kernel PMC of
 # configs 3 and 4.
 #   bash tools/round_final.sh <tag>
@@ -8,7 +8,7 @@ tag=${1:?tag}
 bash tools/gpu_round.sh ${tag} || exit 1
 tail -3 gpurun_out/${tag}_gpu_tests.log
 python3 -c "
-import json; d=json.loads([l for l in open('gpurun_out/${tag}_bench.log') if l.startswith('{')][-1])
+import json; d=json.loads([l for l in open('${OUT_DIR:-_out}/${tag}_bench.log') if l.startswith('{')][-1])
 print('value', round(d['value']/1e6,1), 'ms', round(d['ms_per_step'],3), 'parity', d['parity']['mismatches'], '/', d['parity']['frames'])
 for k,v in (d['extra_configs'] or {}).items(): print(k, round(v['value']/1e6,1), v.get('ms_per_step'))
 "
