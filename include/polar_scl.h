@@ -233,6 +233,8 @@ int pscl_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, int retrie
  * chunks of up to 2^20 frames in handle scratch, counted on the device.  Synchronous.
  *   counters  out, host int64[3][PSCL_NCOUNT]: rows SCL, DL-SCL, uncoded (PSCL_CNT_* layout)
  * Counts depend only on (seed, stream_id, frame range): shards add up exactly.
+ * Rate-matched handles (pscl_set_rate_match(E)) are supported: the TX writes and the decoders read
+ * rows of E LLRs, and rate is then k_payload / E.
  */
 int pscl_simulate(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate, int k_payload,
                   int64_t frame0, int64_t B, int retries, int include_uncoded, int64_t* counters);

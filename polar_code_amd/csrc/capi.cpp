@@ -1800,15 +1800,19 @@ bool tx_fused_applies(const pscl_handle* h, int k_payload) {
 }
 
 // One SNR point of run_sweep enqueued (pscl_simulate / pscl_simulate_device): chunks of at most
-// 2^20 frames through handle scratch (N * 8 bytes of LLRs per frame: about 1 GiB per chunk at
-// N = 128), each = TX (+ the uncoded baseline) + pscl_dlscl_device.  On a pipelined handle every
-// chunk is one pipelined DL-SCL call: its retry chains overlap the next chunk's (or the next
-// point's) TX and baseline, so kDlPar scratch sets rotate with the DL-SCL call parity, and a set
-// is rewritten only after the chains of the call kDlPar back that used it have ended.
+// 2^20 frames through handle scratch (8 bytes per LLR of a row -- N of them, or E on a rate-matched
+// handle: about 1 GiB per chunk at N = 128), each = TX (+ the uncoded baseline) +
+// pscl_dlscl_device.  On a pipelined handle every chunk is one pipelined DL-SCL call: its retry
+// chains overlap the next chunk's (or the next point's) TX and baseline, so kDlPar scratch sets
+// rotate with the DL-SCL call parity, and a set is rewritten only after the chains of the call
+// kDlPar back that used it have ended.
 int simulate_enqueue(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate, int k_payload,
                      int64_t frame0, int64_t B, int retries, int include_uncoded, int64_t* cs) {
     const int64_t chunk = B < (1 << 20) ? B : (1 << 20);
     const int W = h->W, N = h->N;
+    // (a rate-matched handle: the TX launch writes, and dlscl_impl reads, rows of rm_E doubles; the
+    // other scratch of the call -- message and best words, flags, the chains' state -- is per frame)
+    const int64_t row = h->rm_E ? h->rm_E : N;
     int rc;
     for (int64_t f = 0; f < B; f += chunk) {
         const int64_t n = B - f < chunk ? B - f : chunk;
@@ -1823,13 +1827,13 @@ int simulate_enqueue(pscl_handle* h, uint64_t seed, uint32_t stream_id, double e
         // later call of a sweep allocates -- ~130 us of hipMalloc on the host per new set)
         for (int q = h->pipelined ? 0 : par; q <= (h->pipelined ? kDlPar - 1 : par); ++q) {
             const int base = kSimSlot[q];
-            if ((rc = ensure(h, base, (size_t)chunk * N * 8, &d_llr))) return rc;
+            if ((rc = ensure(h, base, (size_t)chunk * row * 8, &d_llr))) return rc;
             if ((rc = ensure(h, base + 1, (size_t)chunk * W * 8, &d_msg))) return rc;
             if ((rc = ensure(h, base + 2, (size_t)chunk * W * 8, &d_best))) return rc;
             if ((rc = ensure(h, base + 3, (size_t)chunk, &d_flags))) return rc;
         }
         const int base = kSimSlot[par];
-        if ((rc = ensure(h, base, (size_t)chunk * N * 8, &d_llr))) return rc;
+        if ((rc = ensure(h, base, (size_t)chunk * row * 8, &d_llr))) return rc;
         if ((rc = ensure(h, base + 1, (size_t)chunk * W * 8, &d_msg))) return rc;
         if ((rc = ensure(h, base + 2, (size_t)chunk * W * 8, &d_best))) return rc;
         if ((rc = ensure(h, base + 3, (size_t)chunk, &d_flags))) return rc;

@@ -14,7 +14,9 @@ FER/BER counters against counts recomputed on the host from the decoded bits.
 Configs 1 and 3 are covered by test_gpu_fer.py (config 1's CSV byte-identical to the
 reference's results/fer_M1.csv, config 3's 4.0-6.5 dB grid); config 3's DL-SCL decode (L = 8,
 beta_M8) is checked here against the oracle at 4.0 and 4.5 dB, and config 4 with every retry
-decode screened.
+decode screened.  The sweep loop that produces configs 3 and 4 (pscl_simulate[_device] as
+run_fer_sweep --rng philox drives it: TX, uncoded baseline, SCL, DL-SCL and the counting in one
+call) is held to the oracle, every counter of every row, by test_gpu_sweep_oracle.py.
 """
 import numpy as np
 import pytest
