@@ -19,6 +19,8 @@
  *   pscl_uncoded_device         <- the uncoded BPSK baseline of run_fer_sweep.py:111-121
  *   pscl_dlscl_device           <- decode_with_retries dl_scl_polar/dlscl/flip.py:65-141 over
  *                                  a device batch (+ pscl_set_beta: the beta checkpoint)
+ *   pscl_adaptive_device        <- sc_decode (polar.py:130-168) + check_crc (crc.py:40-56) on every
+ *                                  frame of a device batch, decode_scl only where that fails
  *   pscl_path_llrs_device       <- best_path_info_llrs / info_llrs of given paths (scl.py:158,166)
  *   pscl_simulate               <- one SNR point of run_sweep (run_fer_sweep.py:41-191): TX,
  *                                  uncoded baseline, SCL + DL-SCL, counters, in one call
@@ -73,6 +75,7 @@ extern "C" {
 #define PSCL_CNT_PAYLOAD_ERR 3 /* frames with >=1 error in the first k_payload bits (run_ber_sweep FER) */
 #define PSCL_CNT_PAYLOAD_BIT 4 /* payload bit errors (run_ber_sweep BER, :77-82) */
 #define PSCL_CNT_RETRIES 5     /* flip re-decodes run by pscl_dlscl_device */
+#define PSCL_CNT_ESCALATED 6   /* frames pscl_adaptive_device handed to the list decode */
 #define PSCL_NCOUNT 8
 
 typedef struct pscl_handle pscl_handle;
@@ -224,6 +227,35 @@ int pscl_set_beta(pscl_handle* h, const double* beta);
 int pscl_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best,
                       uint8_t* d_flags, int32_t* d_attempts, int32_t* d_tried, int tried_stride,
                       const uint64_t* d_ref, int k_payload, int64_t* d_counters_scl, int64_t* d_counters_dl);
+
+/*
+ * Adaptive (list-size-escalating) decode of a device batch: successive cancellation first, the
+ * list decoder only where its result fails the CRC.  Per frame
+ *   1. u = sc_decode(llr, info_set) (dl_scl_polar/polar/polar.py:130-168: f = sign sign min and
+ *      g = b +- a in fp64, frozen leaves 0, information leaves llr < 0); if check_crc(u)
+ *      (crc.py:40-56) holds, the result is u with flags PSCL_FLAG_CRC_PASS | 0 and stage 1;
+ *   2. otherwise the result is pscl_decode_device's for that frame (decode_scl with the handle's
+ *      L and CRC, scl.py:108-209: bits, CRC flag, best index) and the stage is 2.
+ * So the result is the composition of the two reference functions, bit for bit; it is not always
+ * plain SCL's (an SC result that passes the CRC is kept even where the list would rank another
+ * candidate first).  Stage 1 is one lane-parallel SC kernel over all B frames; the escalated rows
+ * are gathered densely into handle scratch, decoded by the handle's plain-decode path (screening
+ * decode plus exact re-decode) and scattered back.  Enqueued on the handle's stream; the call
+ * synchronizes once, after stage 1, to read the escalated count that sizes stage 2 (none is
+ * launched for a count of 0), and returns with stage 2 queued.  Pending pipelined work is ordered
+ * first; the call itself is not pipelined.
+ *   d_best     [B][W] uint64 out;  d_flags [B] uint8 out (both required)
+ *   d_stage    NULL or [B] uint8 out: 1 or 2
+ *   d_ref      NULL or [B][W] transmitted words: the final outputs' statistics are added into
+ *              d_counters as pscl_decode_device adds them, plus the escalated count into
+ *              d_counters[PSCL_CNT_ESCALATED] (d_counters is not touched without d_ref)
+ *   n_escalated NULL or host out: frames handed to stage 2
+ * PSCL_EINVAL without a CRC (every SC result would pass), for B < 0 or d_ref without d_counters;
+ * PSCL_EUNSUP for N != 128.  Rate-matched handles take rows of E LLRs.
+ */
+int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                         uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                         int64_t* n_escalated);
 
 /* Device scratch helpers so that non-torch callers can drive the device path. */
 /*
@@ -435,6 +467,17 @@ int pscl_path_stats(pscl_handle* h, int64_t* fused_post_rounds, int64_t* post_ro
 int pscl_decode_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly, const double* llr, int64_t B,
                     const int8_t* forced, int32_t* n_paths, int8_t* best_bits, uint8_t* crc_pass, int32_t* best_idx,
                     double* metrics, int8_t* cands, double* info_llrs, int threads);
+
+/*
+ * pscl_adaptive_device's contract on the host, without a GPU or a handle: sc_decode
+ * (polar.py:130-168) + check_crc (crc.py:40-56) per frame, and decode_scl (scl.py:108-209, as
+ * pscl_decode_cpu) for the frames that fail.  Any power-of-two N <= PSCL_MAX_N; a CRC is required
+ * (PSCL_EINVAL without one).  best_bits [B][K] int8, crc_pass [B], best_idx [B] (0 at stage 1),
+ * stage [B] (1 or 2); any output may be NULL.  No HIP call is made.
+ */
+int pscl_decode_adaptive_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly, const double* llr,
+                             int64_t B, int8_t* best_bits, uint8_t* crc_pass, int32_t* best_idx, uint8_t* stage,
+                             int threads);
 
 /* Launch geometry used by the decode kernel (for roofline bookkeeping): waves per
  * workgroup, workgroups per launch for B frames, LDS bytes per workgroup. */

@@ -28,6 +28,7 @@ _lib.pscl_decode.argtypes = [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, 
 _lib.pscl_sc_decode.argtypes = [_vp, _vp, _i64, _vp]
 _lib.pscl_set_beta.argtypes = [_vp, _vp]
 _lib.pscl_dlscl_device.argtypes = [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]
+_lib.pscl_adaptive_device.argtypes = [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(_i64)]
 _lib.pscl_device_alloc.argtypes = [_vp, C.POINTER(_vp), _i64]
 _lib.pscl_device_free.argtypes = [_vp, _vp]
 _lib.pscl_memcpy_htod.argtypes = [_vp, _vp, _vp, _i64]
@@ -155,6 +156,31 @@ class SCLDecoder:
                                 p("info_llrs")))
         out["crc_pass"] = out["crc_pass"].astype(bool)
         return out
+
+    def decode_adaptive(self, llr) -> dict:
+        """SC first (polar.py:130-168), the list decode (scl.py:108-209) only for the frames whose SC
+        result fails check_crc: bits [B, K], crc_pass [B], best_idx [B], stage [B] (1 SC, 2 list) and
+        n_escalated.  One pscl_adaptive_device call per batch; N = 128 and a CRC are required."""
+        llr = np.ascontiguousarray(np.asarray(llr, dtype=float))
+        if llr.ndim == 1:
+            llr = llr[None, :]
+        if llr.ndim != 2 or llr.shape[1] != self.N:
+            raise ValueError(f"llr must be [B, {self.N}]")
+        B, K = llr.shape[0], self.K
+        W = (K + 63) // 64 if K else 1
+        n = _i64(0)
+        with _Device(self._h) as dev:
+            d_llr = dev.put(llr)
+            d_best, d_flags, d_stage = dev.alloc(B * W * 8), dev.alloc(B), dev.alloc(B)
+            _check(_lib.pscl_adaptive_device(self._h, d_llr, B, d_best, d_flags, d_stage, None, 0, None, C.byref(n)))
+            _check(_lib.pscl_sync(self._h))
+            words = dev.get(d_best, (B, W), np.uint64)
+            flags = dev.get(d_flags, B, np.uint8)
+            stage = dev.get(d_stage, B, np.uint8)
+        sh = np.arange(64, dtype=np.uint64)
+        bits = ((words[:, :, None] >> sh) & np.uint64(1)).reshape(B, -1)[:, :K].astype(np.int8)
+        return {"bits": bits, "crc_pass": (flags & _FLAG_CRC_PASS) != 0,
+                "best_idx": (flags & _FLAG_IDX_MASK).astype(np.int32), "stage": stage, "n_escalated": int(n.value)}
 
 
 class _Device:

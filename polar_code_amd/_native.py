@@ -30,7 +30,7 @@ PSCL_MAX_L = 32
 PSCL_FLAG_CRC_PASS = 0x80
 PSCL_FLAG_IDX_MASK = 0x3F
 PSCL_NCOUNT = 8
-CNT_FRAMES, CNT_FRAME_ERR, CNT_BIT_ERR, CNT_PAYLOAD_ERR, CNT_PAYLOAD_BIT, CNT_RETRIES = range(6)
+CNT_FRAMES, CNT_FRAME_ERR, CNT_BIT_ERR, CNT_PAYLOAD_ERR, CNT_PAYLOAD_BIT, CNT_RETRIES, CNT_ESCALATED = range(7)
 
 # every symbol the header declares (tests/test_capi_symbols.py checks the .so exports them)
 EXPORTS = (
@@ -43,7 +43,7 @@ EXPORTS = (
     "pscl_screening_count", "pscl_softplus_tails_device", "pscl_set_pipelined", "pscl_join",
     "pscl_tail_abs_scan_device", "pscl_tail2_scan_device", "pscl_set_tuning", "pscl_timing_read_split", "pscl_decode_cpu",
     "pscl_host_stats", "pscl_path_stats",
-    "pscl_simulate_device",
+    "pscl_simulate_device", "pscl_adaptive_device", "pscl_decode_adaptive_cpu",
 )
 
 # pscl_set_tuning knobs (include/polar_scl.h)
@@ -112,6 +112,9 @@ def lib() -> C.CDLL:
                                            _vp]),
         "pscl_decode_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, C.c_int, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, C.c_int]),
+        "pscl_adaptive_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, P(_i64)]),
+        "pscl_decode_adaptive_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, C.c_int, _u64, _vp, _i64, _vp, _vp, _vp, _vp,
+                                               C.c_int]),
         "pscl_timing_read_split": (C.c_int, [_vp, P(_i64), P(_dbl), P(_i64), P(_dbl)]),
         "pscl_host_stats": (C.c_int, [_vp, P(_dbl), P(_dbl), P(_i64), C.c_int]),
         "pscl_path_stats": (C.c_int, [_vp, P(_i64), P(_i64), P(_i64), P(_i64), P(_i64)]),
@@ -293,6 +296,42 @@ class Decoder:
         check(lib().pscl_decode_device(self._h, d_llr, B, d_force or None, d_best or None, d_flags or None,
                                        d_metrics or None, d_cands or None, d_info_llrs or None, d_ref or None,
                                        int(k_payload), d_counters or None))
+
+    def adaptive_device(self, d_llr: int, B: int, *, d_best: int, d_flags: int, d_stage=0, d_ref=0, k_payload=0,
+                        d_counters=0) -> int:
+        """SC first, the list decode only for the frames whose SC result fails the CRC
+        (pscl_adaptive_device; N = 128, a CRC required).  Returns the escalated count."""
+        n = _i64()
+        with self._lock:
+            check(lib().pscl_adaptive_device(self._h, d_llr, int(B), d_best, d_flags, d_stage or None, d_ref or None,
+                                             int(k_payload), d_counters or None, C.byref(n)))
+        return int(n.value)
+
+    def decode_adaptive(self, llr: np.ndarray) -> dict:
+        """Host form of adaptive_device: llr [B, N] (or [B, E]) float64 -> dict(best_bits [B, K] int8,
+        crc_pass [B] bool, best_idx [B] int32, stage [B] uint8 (1 SC, 2 list), n_escalated)."""
+        llr = np.ascontiguousarray(llr, dtype=np.float64)
+        if llr.ndim == 1:
+            llr = llr[None, :]
+        B = llr.shape[0]
+        if llr.shape[1] != (self.E or self.N):
+            raise ValueError("Channel LLR length must be a power of two" if not self.E
+                             else f"expected {self.E} rate-matched LLRs per frame")
+        with DeviceArena(self) as mem:
+            d_llr = mem.alloc(max(llr.nbytes, 8))
+            d_best = mem.alloc(max(B * self.W * 8, 8))
+            d_flags = mem.alloc(max(B, 8))
+            d_stage = mem.alloc(max(B, 8))
+            if B:
+                mem.upload(d_llr, llr)
+            n = self.adaptive_device(d_llr, B, d_best=d_best, d_flags=d_flags, d_stage=d_stage)
+            words = mem.download(d_best, max(B * self.W * 8, 8), np.uint64)[:B * self.W].reshape(B, self.W)
+            flags = mem.download(d_flags, max(B, 8), np.uint8)[:B]
+            stage = mem.download(d_stage, max(B, 8), np.uint8)[:B]
+        j = np.arange(self.K)
+        bits = ((words[:, j >> 6] >> (j & 63).astype(np.uint64)) & np.uint64(1)).astype(np.int8)
+        return {"best_bits": bits, "crc_pass": (flags & PSCL_FLAG_CRC_PASS) != 0,
+                "best_idx": (flags & PSCL_FLAG_IDX_MASK).astype(np.int32), "stage": stage.copy(), "n_escalated": n}
 
     def channel_device(self, seed: int, stream_id: int, ebno_db: float, rate: float, k_payload: int, frame0: int,
                        B: int, d_llr: int, d_msg: int = 0) -> None:
@@ -521,6 +560,22 @@ class CpuDecoder:
                                     _ptr(out["metrics"]), _ptr(out["cands"]), _ptr(out["info_llrs"]), self.threads))
         out["crc_pass"] = out["crc_pass"].astype(bool)
         return out
+
+    def decode_adaptive(self, llr: np.ndarray) -> dict:
+        """Decoder.decode_adaptive on the host (pscl_decode_adaptive_cpu), same keys."""
+        llr = np.ascontiguousarray(llr, dtype=np.float64)
+        if llr.ndim == 1:
+            llr = llr[None, :]
+        B = llr.shape[0]
+        if llr.shape[1] != self.N:
+            raise ValueError("Channel LLR length must be a power of two")
+        bits = np.zeros((B, self.K), np.int8)
+        ok, idx, stage = np.zeros(B, np.uint8), np.zeros(B, np.int32), np.zeros(B, np.uint8)
+        check(lib().pscl_decode_adaptive_cpu(self.N, self.info_set.ctypes.data_as(C.POINTER(_i32)), self.K, self.L,
+                                             self.crc_poly, _ptr(llr), B, _ptr(bits), _ptr(ok), _ptr(idx), _ptr(stage),
+                                             self.threads))
+        return {"best_bits": bits, "crc_pass": ok.astype(bool), "best_idx": idx, "stage": stage,
+                "n_escalated": int(np.count_nonzero(stage == 2))}
 
     def sync(self) -> None:
         pass

@@ -143,6 +143,7 @@ struct pscl_handle {
     hipEvent_t ev_scr[kChainStreams] = {}, ev_def[kChainStreams] = {};
     hipEvent_t ev_base[kDlPar] = {}, ev_retry[kDlPar] = {}, ev_join[kChainSets] = {};
     int32_t* h_count = nullptr;          // pinned: failing-frame counts of the chunk parities
+    int32_t* h_adapt = nullptr;          // pinned: escalated-frame count of pscl_adaptive_device
     double* d_beta = nullptr;         // [K][K] DL-SCL flip metric (null = |L0|)
     float* d_beta32g[2] = {nullptr, nullptr};  // K = 64: fp32 beta, [K][G][K / G] for G = 8, 4 (fused post)
     std::vector<float> beta32g_host;
@@ -744,6 +745,7 @@ int pscl_destroy(pscl_handle* h) {
     for (int i = 0; i < kChainSets; ++i)
         if (h->ev_join[i]) hipEventDestroy(h->ev_join[i]);
     if (h->h_count) hipHostFree(h->h_count);
+    if (h->h_adapt) hipHostFree(h->h_adapt);
     for (int i = 0; i < kChainStreams; ++i) {
         if (h->side_stream[i]) hipStreamSynchronize(h->side_stream[i]);
         if (h->retry_stream[i]) hipStreamDestroy(h->retry_stream[i]);
@@ -816,6 +818,106 @@ int pscl_decode_device(pscl_handle* h, const double* d_llr, int64_t B, const uin
     if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
     if (!h->pipelined && (rc = join_pipe(h))) return rc;
     return launch_decode(h, P, hist, nullptr, 38, h->pipelined);
+}
+
+// Adaptive decode (include/polar_scl.h): stage 1 is the lane-parallel SC kernel over all B frames;
+// the frames whose SC result fails the CRC are compacted (dl_compact on the flags), their rows
+// gathered densely into scratch, decoded by launch_decode as a plain decode of that many frames --
+// the screening path, not a row list, which would land on the exact kernel -- and scattered back.
+// Scratch slots 72..76: count, frame list, dense rows, dense best words, dense flags.  One host
+// wait, after stage 1: the escalated count sizes the dense batch.
+int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                         uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                         int64_t* n_escalated) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (n_escalated) *n_escalated = 0;
+    if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
+    if (!h->crc_poly) return fail(PSCL_EINVAL, "adaptive decoding needs a CRC (without one every SC result passes)");
+    if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
+    if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
+    if (h->N != PSCL_FAST_N)
+        return fail(PSCL_EUNSUP, "adaptive decoding is implemented for N = %d only (N = %d)", PSCL_FAST_N, h->N);
+    if (B == 0) return PSCL_OK;
+    if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
+    if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
+    int rc = enter(h);  // (pending pipelined work first; the call runs stream-ordered)
+    if (rc) return rc;
+    const int W = h->W;
+    const int64_t row = h->rm_E ? h->rm_E : h->N;
+    hipStream_t s = h->stream;
+    hipError_t e;
+    if (!h->h_adapt) HIP_TRY(hipHostMalloc((void**)&h->h_adapt, 4, hipHostMallocDefault));
+    void *d_cnt, *d_act;
+    if ((rc = ensure(h, 72, 4, &d_cnt))) return rc;
+    if ((rc = ensure(h, 73, (size_t)B * 8, &d_act))) return rc;
+    // stage 1
+    pscl_sc_params S;
+    memset(&S, 0, sizeof(S));
+    S.llr = d_llr;
+    S.B = B;
+    S.K = h->K;
+    S.W = W;
+    S.info_mask[0] = h->info_mask[0];
+    S.info_mask[1] = h->info_mask[1];
+    S.epi_table = h->d_epi;
+    S.epi_words = h->epi_words;
+    S.rm_E = h->rm_E;
+    S.rm_src = h->d_rm_src;
+    S.best = d_best;
+    S.flags = d_flags;
+    S.stage = d_stage;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->timing) {  // (the SC launch is one timed launch on the handle's stream, like a decode)
+        while (h->ev_pool.size() < h->ev_used + 2) {
+            hipEvent_t ev;
+            HIP_TRY(hipEventCreate(&ev));
+            h->ev_pool.push_back(ev);
+        }
+        e0 = h->ev_pool[h->ev_used];
+        e1 = h->ev_pool[h->ev_used + 1];
+        if (h->ev_main.size() < h->ev_pool.size() / 2) h->ev_main.resize(h->ev_pool.size() / 2);
+        h->ev_main[h->ev_used / 2] = 1;
+        h->ev_used += 2;
+        HIP_TRY(hipEventRecord(e0, s));
+    }
+    if ((e = pscl_launch_sc_lane(S, s)) != hipSuccess) return fail(PSCL_EDEVICE, "sc kernel launch: %s", hipGetErrorString(e));
+    if (h->timing) HIP_TRY(hipEventRecord(e1, s));
+    // the failing frames and their count
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 4, s));
+    if ((e = pscl_launch_dl_compact(d_flags, B, 0, (int64_t*)d_act, nullptr, (int32_t*)d_cnt, s)) != hipSuccess)
+        return fail(PSCL_EDEVICE, "dl_compact launch: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(h->h_adapt, d_cnt, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the call's one host wait
+    const int64_t n = *h->h_adapt;
+    if (n < 0 || n > B) return fail(PSCL_EDEVICE, "escalated count %lld out of range", (long long)n);
+    if (n_escalated) *n_escalated = n;
+    if (n > 0) {
+        // stage 2: a plain decode of the dense batch
+        void *d_rows, *d_b2, *d_f2;
+        if ((rc = ensure(h, 74, (size_t)n * (size_t)row * 8, &d_rows))) return rc;
+        if ((rc = ensure(h, 75, (size_t)n * W * 8, &d_b2))) return rc;
+        if ((rc = ensure(h, 76, (size_t)n, &d_f2))) return rc;
+        if ((e = pscl_launch_gather_rows(d_llr, row, (const int64_t*)d_act, n, (double*)d_rows, s)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "gather launch: %s", hipGetErrorString(e));
+        pscl_decode_params P;
+        fill_decode_params(h, P, 0);
+        P.llr = (const double*)d_rows;
+        P.B = n;
+        P.best = (uint64_t*)d_b2;
+        P.flags = (uint8_t*)d_f2;
+        if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
+        if ((rc = launch_decode(h, P, 0))) return rc;
+        if ((e = pscl_launch_scatter_results((const int64_t*)d_act, n, W, (const uint64_t*)d_b2, (const uint8_t*)d_f2, d_best,
+                                             d_flags, s)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "scatter launch: %s", hipGetErrorString(e));
+    }
+    if (d_ref) {  // statistics of the final outputs, as a plain decode adds them, and the escalated count
+        if ((e = pscl_launch_dl_count(d_best, d_flags, d_ref, B, W, k_payload, d_counters, s)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "dl_count launch: %s", hipGetErrorString(e));
+        if (n > 0 && (e = pscl_launch_add_counter(d_counters, PSCL_CNT_ESCALATED, n, s)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "counter launch: %s", hipGetErrorString(e));
+    }
+    return PSCL_OK;
 }
 
 int pscl_join(pscl_handle* h) {

@@ -181,7 +181,71 @@ struct CpuScl {
     }
 };
 
+// sc_decode's recursion (polar.py:146-164) over one segment of w LLRs from phase `start`: the
+// decided bits go to u, the segment's partial sums (combined, polar.py:163) to x[0, w); work holds
+// the child segments (w values are enough for the whole descent)
+void sc_segment(const double* seg, int w, int start, const uint8_t* is_info, double* work, uint8_t* u, uint8_t* x) {
+    if (w == 1) {
+        const uint8_t bit = is_info[start] ? (uint8_t)(seg[0] < 0.0) : (uint8_t)0;
+        u[start] = bit;
+        x[0] = bit;
+        return;
+    }
+    const int h = w / 2;
+    for (int i = 0; i < h; ++i) work[i] = f_node(seg[i], seg[i + h]);
+    sc_segment(work, h, start, is_info, work + h, u, x);
+    for (int i = 0; i < h; ++i) work[i] = g_node(seg[i], seg[i + h], x[i]);
+    sc_segment(work, h, start + h, is_info, work + h, u, x + h);
+    for (int i = 0; i < h; ++i) x[i] ^= x[i + h];
+}
+
 }  // namespace
+
+// SC first, the list decoder where its result fails the CRC (pscl_adaptive_device's contract)
+extern "C" int pscl_decode_adaptive_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly,
+                                        const double* llr, int64_t B, int8_t* best_bits, uint8_t* crc_pass,
+                                        int32_t* best_idx, uint8_t* stage, int threads) {
+    if (N < 2 || N > PSCL_MAX_N || (N & (N - 1))) return PSCL_EINVAL;
+    if (L < 1 || L > 255 || K < 0 || K > N || B < 0 || (B && !llr) || (K && !info_set)) return PSCL_EINVAL;
+    for (int i = 0; i < K; ++i)
+        if (info_set[i] < 0 || info_set[i] >= N || (i && info_set[i] <= info_set[i - 1])) return PSCL_EINVAL;
+    if (!crc_poly) return PSCL_EINVAL;  // (without a CRC every SC result would pass)
+    const int deg = 63 - __builtin_clzll(crc_poly);
+    if (deg <= 0 || K <= deg) return PSCL_EINVAL;
+    if (B == 0) return PSCL_OK;
+    int T = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    if (T < 1) T = 1;
+    if ((int64_t)T > B) T = (int)B;
+    auto work = [&](int t) {
+        CpuScl dec(N, info_set, K, L, crc_poly);
+        std::vector<double> tmp((size_t)N);
+        std::vector<uint8_t> u((size_t)N), x((size_t)N), bits((size_t)(K ? K : 1));
+        const int64_t b0 = B * t / T, b1 = B * (t + 1) / T;
+        for (int64_t b = b0; b < b1; ++b) {
+            sc_segment(llr + b * N, N, 0, dec.is_info.data(), tmp.data(), u.data(), x.data());
+            for (int i = 0; i < K; ++i) bits[(size_t)i] = u[(size_t)info_set[i]];
+            if (dec.crc_ok(bits.data())) {
+                if (best_bits)
+                    for (int i = 0; i < K; ++i) best_bits[b * K + i] = (int8_t)bits[(size_t)i];
+                if (crc_pass) crc_pass[b] = 1;
+                if (best_idx) best_idx[b] = 0;
+                if (stage) stage[b] = 1;
+            } else {
+                dec.decode(llr + b * N, nullptr, nullptr, best_bits ? best_bits + b * K : nullptr,
+                           crc_pass ? crc_pass + b : nullptr, best_idx ? best_idx + b : nullptr, nullptr, nullptr, nullptr);
+                if (stage) stage[b] = 2;
+            }
+        }
+    };
+    if (T == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < T; ++t) pool.emplace_back(work, t);
+        for (auto& th : pool) th.join();
+    }
+    return PSCL_OK;
+}
 
 extern "C" int pscl_decode_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly, const double* llr,
                                int64_t B, const int8_t* forced, int32_t* n_paths, int8_t* best_bits, uint8_t* crc_pass,

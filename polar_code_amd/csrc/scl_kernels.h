@@ -247,6 +247,33 @@ struct pscl_channel_params {
     const int32_t* rm_order;     // [N] sub-block interleaver order
 };
 
+// Lane-parallel successive cancellation of the N = 128 codes (sc128_lane.hip): stage 1 of
+// pscl_adaptive_device.  Frame b's hard-decision SC result (polar.py:130-168) goes to best / flags
+// (PSCL_FLAG_CRC_PASS | 0 when check_crc holds, else 0) and stage (1 pass, 2 fail).
+struct pscl_sc_params {
+    const double* llr;           // [B][128] (or [B][rm_E] with rate matching)
+    int64_t B;
+    int K, W;
+    uint64_t info_mask[2];       // bit phi set <=> phase phi is an information bit
+    const uint64_t* epi_table;   // the scl128 epilogue tables (pscl_decode_params::epi_table)
+    int epi_words;
+    int rm_E;
+    const int32_t* rm_src;
+    uint64_t* best;              // [B][W]
+    uint8_t* flags;              // [B]
+    uint8_t* stage;              // [B] or null
+};
+int pscl_sc_lane_lds(const pscl_sc_params& P);
+int64_t pscl_sc_lane_grid(const pscl_sc_params& P);
+hipError_t pscl_launch_sc_lane(const pscl_sc_params& P, hipStream_t s);
+// the hand-off of pscl_adaptive_device: rows act[i] (i < n) of llr gathered densely, and the dense
+// results scattered back to rows act[i]; counters[PSCL_CNT_ESCALATED] += n
+hipError_t pscl_launch_gather_rows(const double* llr, int64_t row, const int64_t* act, int64_t n, double* out,
+                                   hipStream_t s);
+hipError_t pscl_launch_scatter_results(const int64_t* act, int64_t n, int W, const uint64_t* best_in,
+                                       const uint8_t* flags_in, uint64_t* best, uint8_t* flags, hipStream_t s);
+hipError_t pscl_launch_add_counter(int64_t* counters, int slot, int64_t v, hipStream_t s);
+
 int pscl_decode_lmax(int L);
 // scl_long.hip (N = 256 .. 1024)
 int64_t pscl_long_block_bytes(int N, int L, int K, int hist);

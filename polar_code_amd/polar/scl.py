@@ -114,5 +114,35 @@ class SCLDecoder:
             d_counters=counters.data_ptr() if counters is not None else 0)
         return best, flags
 
+    def decode_adaptive(self, llr: np.ndarray) -> dict:
+        """SC first, the list decode only for the frames whose SC result fails the CRC
+        (pscl_adaptive_device): bits [B, K] int8, crc_pass [B] bool, best_idx [B], stage [B]
+        (1 SC, 2 list) and n_escalated.  N = 128 and a CRC are required."""
+        out = self._dec.decode_adaptive(llr)
+        out["bits"] = out.pop("best_bits")
+        return out
+
+    def decode_tensor_adaptive(self, llr, ref_words=None, k_payload: int = 0, counters=None):
+        """Device path of decode_adaptive on the caller's current torch stream, mirroring
+        decode_tensor: returns (best_words [B, W] int64, flags [B] uint8, stage [B] uint8) tensors;
+        with ref_words the final outputs' error statistics and the escalated count are added
+        into `counters` (int64[8] tensor).  The call waits once on the host, after the SC stage."""
+        import torch
+
+        row = self._dec.E or self.N
+        if llr.dtype != torch.float64 or not llr.is_contiguous() or llr.dim() != 2 or llr.shape[1] != row:
+            raise ValueError("llr must be a contiguous float64 [B, N] tensor")
+        B = llr.shape[0]
+        W = self._dec.W
+        best = torch.empty((B, W), dtype=torch.int64, device=llr.device)
+        flags = torch.empty((B,), dtype=torch.uint8, device=llr.device)
+        stage = torch.empty((B,), dtype=torch.uint8, device=llr.device)
+        self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
+        self._dec.adaptive_device(
+            llr.data_ptr(), B, d_best=best.data_ptr(), d_flags=flags.data_ptr(), d_stage=stage.data_ptr(),
+            d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
+            d_counters=counters.data_ptr() if counters is not None else 0)
+        return best, flags, stage
+
 
 __all__ = ["decode_scl", "SCLDecoder"]
