@@ -63,6 +63,92 @@ def test_cpu_n256():
     assert out["n_escalated"] == exp["n_escalated"]
 
 
+def test_block_family_enters_every_sc_node_in_every_state(golden):
+    """The SC kernel's only branches are its mask tests: 127 nodes, each entered with information
+    in both halves, in the right half only or in the left half only.  The block family covers all
+    381 pairs; the constructed sets cover no "left only" pair at all (position i + M/2 is never
+    less reliable than position i), which is why the family exists."""
+    every = ac.all_branch_states()
+    assert len(every) == 381
+    fam = ac.block_family()
+    assert len(fam) == 14 and all(len(s) == 64 and np.all(np.diff(s) > 0) for _, s in fam)
+    np.testing.assert_array_equal(dict(fam)["bit6=0"], np.arange(0, 64))
+    np.testing.assert_array_equal(dict(fam)["bit6=1"], np.arange(64, 128))
+    covered = set().union(*(ac.sc_branch_states(s) for _, s in fam))
+    print(f"block family: {len(covered & every)} of {len(every)} (node, state) pairs")
+    assert covered == every
+    g1 = golden("g1_info_sets.npz")
+    built = [s for _, s in ac.edge_family()[:4]] + [ac.info_set(128, K) for K in (40, 64, 88)]
+    built += [g1["info_128_64"], g1["info_128_88"]]
+    got = set().union(*(ac.sc_branch_states(s) for s in built))
+    assert got <= every and not [st for st in got if st[2] and not st[3]]
+    assert len(ac.family()) == 19 and len({n for n, _ in ac.family()}) == 19
+    assert [len(s) for _, s in ac.edge_family()] == [27, 63, 65, 90, 64]
+
+
+@pytest.mark.parametrize("name", [n for n, _ in ac.family()])
+def test_cpu_every_branch_state(name):
+    """The host form on the 19 sets, B = 256, L = 4: the composition on the raw rows, and on the
+    shifted rows (the oracle's SC result is a random CRC-valid word on every one) exactly the
+    targets from stage 1."""
+    case = ac.family_case(name)
+    info, B = case["info"], 256
+    dec = _native.CpuDecoder(128, info, 4, ac.POLY24)
+    out = dec.decode_adaptive(case["raw"][:B])
+    ac.assert_equals(out, case["exp"], f"cpu {name} raw", slice(0, B))
+    assert out["n_escalated"] == int(np.count_nonzero(~case["exp"]["sc_ok"][:B]))
+    out = dec.decode_adaptive(case["shifted"][:B])
+    np.testing.assert_array_equal(out["best_bits"], case["t"][:B])
+    assert np.all(out["stage"] == 1) and np.all(out["crc_pass"]) and out["n_escalated"] == 0
+
+
+def _sc_model(llr, mask, S, bad, u):
+    """sc_decode in plain Python with the kernel's sub-tree skips; the node in state `bad` =
+    (M, S, left, right) is mishandled: its g sees the left partial sums inverted (both halves; right
+    only: the skipped half's zeros as ones), or it hands its own sums up inverted (left only)."""
+    M = len(llr)
+    if M == 1:
+        u[S] = int(llr[0] < 0)
+        return np.array([u[S]], np.int8)
+    h = M // 2
+    left, right = bool(mask[S:S + h].any()), bool(mask[S + h:S + M].any())
+    hit = bad == (M, S, left, right)
+    a, b = llr[:h], llr[h:]
+    xl, xr = np.zeros(h, np.int8), np.zeros(h, np.int8)
+    if left:
+        xl = _sc_model(np.sign(a) * np.sign(b) * np.minimum(np.abs(a), np.abs(b)), mask, S, bad, u)
+    if right:
+        xs = 1 - xl if hit else xl
+        xr = _sc_model(b + (1 - 2 * xs) * a, mask, S + h, bad, u)
+    elif hit:
+        xl = 1 - xl
+    return np.concatenate([xl ^ xr, xr])
+
+
+def test_shifted_rows_observe_every_branch_state():
+    """What the shifted rows can see, on the host: with any one (node, state) pair mishandled, the
+    model's bits differ from the targets on some row of a block set that enters the pair.  The
+    exceptions are the seven "left only" nodes on the tree's right edge, whose partial sums no g
+    ever reads."""
+    cases = [ac.family_case(n) for n, _ in ac.block_family()]
+    masks = []
+    for c in cases:
+        m = np.zeros(128, bool)
+        m[c["info"]] = True
+        masks.append(m)
+
+    def differs(c, mask, bad, r):
+        u = np.zeros(128, np.int8)
+        _sc_model(c["shifted"][r], mask, 0, bad, u)
+        return not np.array_equal(u[c["info"]], c["t"][r])
+
+    assert not any(differs(c, m, None, r) for c, m in zip(cases, masks) for r in range(3))  # the model itself
+    blind = [p for p in sorted(ac.all_branch_states())
+             if not any(differs(c, m, p, r) for c, m in zip(cases, masks) if p in ac.sc_branch_states(c["info"])
+                        for r in range(8))]
+    assert blind == [(M, 128 - M, True, False) for M in (2, 4, 8, 16, 32, 64, 128)]
+
+
 def test_cpu_requires_a_crc():
     dec = _native.CpuDecoder(128, ac.info_set(128, 64), 8, None)
     with pytest.raises(ValueError):

@@ -69,9 +69,8 @@ def test_every_frame_escalates(dec8):
 
 def test_nr_rate_matched():
     info, E, B = ac.info_set(128, 88), 256, 2051
-    rows = ac.make_llr(77, B, info, ac.POLY24, 5.0, E=E)
-    exp = ac.compose(rows, info, 8, ac.POLY24, E=E)
-    assert 0 < exp["n_escalated"] < B  # (the oracle: 920 SC passes)
+    rows, exp = ac.nr_case()
+    assert rows.shape == (B, E) and 0 < exp["n_escalated"] < B  # (the oracle: 920 SC passes)
     dec = _native.Decoder(128, info, 8, ac.POLY24)
     dec.set_rate_match(E)
     _check(dec, rows, exp, "NR (128,88) E=256")
@@ -143,6 +142,119 @@ def test_exact_arithmetic_corners_in_stage_1(golden, dec8):
     out = dec8.decode_adaptive(rows)
     assert out["n_escalated"] == 0 and np.all(out["stage"] == 1) and np.all(out["crc_pass"])
     np.testing.assert_array_equal(out["best_bits"], sc)
+
+
+def _stage1_decides(dec, rows, t, tag):
+    out = dec.decode_adaptive(rows)
+    np.testing.assert_array_equal(out["best_bits"], t, err_msg=f"{tag}: stage-1 bits")
+    assert np.all(out["crc_pass"]), tag
+    assert np.all(out["stage"] == 1) and np.all(out["best_idx"] == 0) and out["n_escalated"] == 0, tag
+
+
+@pytest.mark.parametrize("name", [n for n, _ in ac.family()])
+def test_every_branch_state(name):
+    """The 14 block sets (every SC node in each of its three states, the root skips, full and empty
+    mask words, the lane offsets 0, 32, 32, 64) and the 5 edge sets (K = 27, 63, 65, 90: partial
+    syndrome nibbles, one and two output words; the mirrored (128,64) set), B = 256 + 3, L = 4.  On
+    the shifted rows stage 1 decides every frame and its bits are the random CRC-valid targets; the
+    raw rows equal the composition (there the runtime-information-set list kernel runs, and for
+    K = 65, 90 the gather and scatter with two words)."""
+    case = ac.family_case(name)
+    B = len(case["raw"])
+    assert B == 259 and case["t"].any(axis=1).sum() > B // 2  # (K = 27 has 3 payload bits: some targets are zero)
+    dec = _native.Decoder(128, case["info"], 4, ac.POLY24)
+    _stage1_decides(dec, case["shifted"], case["t"], f"{name} shifted")
+    _check(dec, case["raw"], case["exp"], f"{name} raw")
+
+
+@pytest.mark.parametrize("E", [200, 256])
+def test_rate_matched_front_end_on_a_block_set(E):
+    """A set that is not reliability ordered behind the rate-matched front end.  E = 200: one
+    repeat plus a remainder of 72, the de-rate-match's means over 2 values and over 1; E = 256:
+    every mean over 2.  The rows are shifted through the TX chain so that stage 1 decides."""
+    info, B = ac.family_set("bit3=0"), 259
+    raw = ac.make_llr(600 + E, B, info, ac.POLY24, 5.0, E=E)
+    rows, t = ac.shift_to_valid(raw, info, ac.POLY24, seed=700 + E, E=E)
+    dec = _native.Decoder(128, info, 4, ac.POLY24)
+    dec.set_rate_match(E)
+    _stage1_decides(dec, rows, t, f"bit3=0 E={E} shifted")
+    _check(dec, raw, ac.compose(raw, info, 4, ac.POLY24, E=E), f"bit3=0 E={E} raw")
+
+
+def _source_ints(pattern, what):
+    """Integers of the SC source, by pattern -- failing loudly when the pattern is gone, so that a
+    change of a grid cap cannot quietly leave these tests inside one grid pass."""
+    import re
+    from pathlib import Path
+
+    src = (Path(_native.__file__).resolve().parent / "csrc" / "sc128_lane.hip").read_text()
+    m = re.search(pattern, src, re.S)
+    assert m, f"sc128_lane.hip: {what} not found; update the pattern with the kernel"
+    return [int(g) for g in m.groups()]
+
+
+def _frames_per_grid_pass(rm):
+    cap, cap2 = _source_ints(r"int64_t pscl_sc_lane_grid\([^{]*\{.*?if \(grid > (\d+)\) grid = (\d+);", "the SC grid cap")
+    (fpw,) = _source_ints(r"constexpr int kFramesPerWave = (\d+);", "frames per wavefront")
+    w_rm, w_plain = _source_ints(r"constexpr int wavesPerWg\(bool rm\) \{ return rm \? (\d+) : (\d+); \}", "wavefronts per workgroup")
+    assert cap == cap2
+    return cap * fpw * (w_rm if rm else w_plain)
+
+
+def _timed_tiled(dec, rows, exp, reps, tag):
+    import time
+
+    t0 = time.perf_counter()
+    big = np.tile(rows, (reps, 1))
+    want = ac.tiled(exp, reps)
+    t1 = time.perf_counter()
+    out = dec.decode_adaptive(big)
+    t2 = time.perf_counter()
+    ac.assert_equals(out, want, tag)
+    assert out["n_escalated"] == want["n_escalated"], tag
+    print(f"{tag}: B = {len(big)}, {out['n_escalated']} escalated; tile {t1 - t0:.3f} s, "
+          f"upload + decode + unpack {t2 - t1:.3f} s, compare {time.perf_counter() - t2:.3f} s")
+    return out
+
+
+def test_plain_rows_past_the_grid_cap(dec8):
+    """B = 33 * 4099 = 135267 > 2048 * 64: the frame loop's second iteration (workgroups 0..65)."""
+    reps = 33
+    B = reps * len(ac.mixed_rows())
+    per_pass = _frames_per_grid_pass(False)
+    assert B == 135267 and B > per_pass, (B, per_pass)
+    _timed_tiled(dec8, ac.mixed_rows(), ac.mixed_expected(8), reps, "plain, two grid passes")
+
+
+def test_rate_matched_rows_past_the_grid_cap():
+    """B = 40 * 2051 = 82040 > 2048 * 32: about 16.5 k frames (516 workgroups) take the second
+    iteration, which reuses the wavefront's LDS staging rows behind the second fence."""
+    reps = 40
+    rows, exp = ac.nr_case()
+    B = reps * len(rows)
+    per_pass = _frames_per_grid_pass(True)
+    assert B == 82040 and B - per_pass > 16000, (B, per_pass)
+    dec = _native.Decoder(128, ac.info_set(128, 88), 8, ac.POLY24)
+    dec.set_rate_match(256)
+    _timed_tiled(dec, rows, exp, reps, "rate matched, two grid passes")
+
+
+def test_gather_past_its_grid_cap(dec8):
+    """Every one of B = 132000 frames escalates: n * 128 values exceed the gather kernel's
+    65536 * 256 threads, so its grid-stride loop takes a second step; results are plain L = 8's."""
+    reps = 132
+    rows, exp = ac.allfail_case()
+    B = reps * len(rows)
+    per, cap, cap2, per2 = _source_ints(
+        r"pscl_launch_gather_rows\([^{]*\{.*?\(n \* row \+ \d+\) / (\d+);\s*if \(grid > (\d+)\) grid = (\d+);.*?dim3\((\d+)\), 0, s, llr",
+        "the gather kernel's grid cap")
+    assert per == per2 and cap == cap2  # (threads per block; blocks)
+    assert B == 132000 and exp["n_escalated"] == len(rows) and B * 128 > cap * per, (B, cap, per)
+    out = _timed_tiled(dec8, rows, exp, reps, "all escalate, gather stride")
+    assert out["n_escalated"] == B and np.all(out["stage"] == 2)
+    np.testing.assert_array_equal(out["best_bits"], np.tile(exp["list_bits"], (reps, 1)))
+    np.testing.assert_array_equal(out["best_idx"], np.tile(exp["list_idx"], reps))
+    np.testing.assert_array_equal(out["crc_pass"], np.tile(exp["list_ok"], reps))
 
 
 def test_counters_with_reference(dec8):
