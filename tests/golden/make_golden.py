@@ -22,9 +22,12 @@ Fixture sets:
   G13 train_beta on the G12 shard (CPU, one thread): beta + log      train/train_beta.py:64-161
   G14 longer codes: decode_scl at N in {256, 512, 1024} (incl. forced bits) and sc_decode at N=256
   G15 decode_with_retries on quantised LLRs (exact |L0| / q ties in the flip ranking)  flip.py:104-108
+  G16 decode_with_retries off the (128,64) code: N in {4..64}, K = N, (128,88), (128,100), short CRCs,
+      retries >= K; beta random fp32 and None, tie-guarded (one shape: `make_golden.py g16`)         flip.py:65-141
 """
 from __future__ import annotations
 
+import hashlib
 import sys
 from pathlib import Path
 
@@ -375,6 +378,125 @@ def g15():
     np.savez_compressed(OUT / "g15_dl_ties.npz", **d)
 
 
+# (N, K, CRC polynomial, M, retries, Eb/N0 in dB): the DL-SCL loop off the compiled-in (128,64) code.
+# Eb/N0 per case puts the baseline's failure share between 10 % and 60 % of the drawn frames.
+G16_CASES = [(64, 40, "0x1864CFB", 4, 8, 2.0), (32, 20, "0x107", 2, 24, 2.0), (32, 28, "0x1864CFB", 4, 6, 1.5),
+             (16, 12, "0x43", 1, 4, 1.5), (8, 6, "0xB", 2, 6, -2.0), (4, 3, "0x7", 2, 3, -8.0),
+             (64, 64, "0x1864CFB", 8, 5, 3.5), (128, 88, "0x1864CFB", 8, 6, 2.75), (128, 100, "0x1864CFB", 4, 6, 4.0)]
+G16_FAIL, G16_PASS, G16_TIE_REL = 12, 4, 1e-9
+G16_FIELDS = ("info", "llr", "msg", "beta_bits", "beta_success", "beta_attempts", "beta_tried",
+              "none_bits", "none_success", "none_attempts", "none_tried")
+
+
+def g16_tag(N, K):
+    return f"n{N}k{K}"
+
+
+def save_stable(path, d):
+    """np.savez_compressed with fixed member timestamps: the same arrays give the same bytes."""
+    import io
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for key, val in d.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(val), allow_pickle=False)
+            zi = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o600 << 16
+            z.writestr(zi, buf.getvalue())
+
+
+def g16_untied(r, beta):
+    """Tie guard: at every round the chosen q (recomputed from that attempt's best_path_info_llrs,
+    flip.py:102-108,133) lies below every other untried q by more than G16_TIE_REL relative."""
+    tried = r["tried_indices"]
+    for rnd, idx in enumerate(tried):
+        a = np.abs(np.asarray(r["attempts"][rnd]["best_path_info_llrs"], dtype=float))
+        q = a @ beta if beta is not None else a
+        for o in range(q.size):
+            if o == idx or o in tried[:rnd]:
+                continue
+            if not q[o] - q[idx] > G16_TIE_REL * max(abs(q[o]), abs(q[idx])):
+                return False
+    return True
+
+
+def g16():
+    """decode_with_retries on short and odd shapes (N < 128, K = N, short CRCs, retries >= K, and the
+    N = 128 codes whose K is not 64), beta random fp32 and None; no flip choice at a tie."""
+    tags = [g16_tag(N, K) for N, K, *_ in G16_CASES]
+    d, table, sha = {}, [], []
+    seen = {"first": 0, "later": 0, "exhausted": 0, "all_k": 0}
+    for ci, (N, K, crc, M, retries, ebno) in enumerate(G16_CASES):
+        tag = g16_tag(N, K)
+        info = construct_info_set(N, K)
+        rng = np.random.default_rng(1600 + ci)
+        beta = rng.random((K, K)).astype(np.float32)  # (the seeded stream's first draw; fp32 as the reference stores it)
+        deg = len(bin(int(crc, 16))) - 3
+        kept, nfail, npass, drawn, failed, dropped = [], 0, 0, 0, 0, 0
+        while nfail < G16_FAIL or npass < G16_PASS:
+            msg = attach_crc(rng.integers(0, 2, size=K - deg, dtype=np.int8), crc)
+            u = np.zeros(N, np.int8)
+            u[info] = msg
+            llr = llr_awgn(rng, _polar_transform(u), ebno, K / N)
+            bad = not check_crc(decode_scl(llr, info, M, crc=crc)["best_path_bits"], crc)
+            drawn += 1
+            failed += bad
+            if (nfail >= G16_FAIL) if bad else (npass >= G16_PASS):
+                continue
+            res = [decode_with_retries(llr, info, M, retries, crc=crc, beta=b) for b in (beta, None)]
+            if not (g16_untied(res[0], beta) and g16_untied(res[1], None)):
+                dropped += 1
+                continue
+            kept.append((llr, msg, res))
+            nfail += bad
+            npass += not bad
+        assert 0.10 <= failed / drawn <= 0.60, (tag, failed, drawn)
+        # (the nine random fp32 matrices alone are 98 KB incompressible: the file holds each one's seed
+        # and SHA-256, and tests/dl_short_cases.py g16_beta() repeats the draw above, checked by the hash)
+        table.append([N, K, int(crc, 16), M, retries, len(kept), 1600 + ci, dropped, drawn, failed])
+        sha.append(hashlib.sha256(beta.tobytes()).hexdigest())
+        d[f"{tag}_info"] = info
+        d[f"{tag}_llr"] = np.stack([k[0] for k in kept])
+        d[f"{tag}_msg"] = np.stack([k[1] for k in kept])
+        for w, name in enumerate(("beta", "none")):
+            rs = [k[2][w] for k in kept]
+            tried = np.full((len(rs), retries), -1, np.int32)
+            for f, r in enumerate(rs):
+                t = r["tried_indices"]
+                tried[f, : len(t)] = t
+                if r["success"] and len(t) == 1:
+                    seen["first"] += 1
+                if r["success"] and len(t) > 1:
+                    seen["later"] += 1
+                if not r["success"]:
+                    assert len(t) == min(retries, K), (tag, f)
+                    seen["exhausted"] += 1
+                if retries >= K and len(t) == K:
+                    assert sorted(t) == list(range(K))
+                    seen["all_k"] += 1
+            d[f"{tag}_{name}_bits"] = np.stack([r["best_path_bits"] for r in rs]).astype(np.int8)
+            d[f"{tag}_{name}_success"] = np.array([r["success"] for r in rs])
+            d[f"{tag}_{name}_attempts"] = np.array([len(r["attempts"]) for r in rs], np.int32)
+            d[f"{tag}_{name}_tried"] = tried
+        print(tag, "drawn", drawn, "failed", failed, "dropped", dropped)
+    # outcome coverage over the family: rescued at the first flip, rescued later, exhausted and still
+    # failing, every one of the K indices tried (a retries >= K case)
+    assert all(v > 0 for v in seen.values()), seen
+    print("g16 outcomes", seen)
+    # one flat array per field over the cases, in G16_CASES order (a zip member per case and field
+    # costs more than the small cases hold); `table` gives each case's shape, tests/dl_short_cases.py
+    # unpacks.  table columns: N, K, CRC polynomial, M, retries, frames, beta seed, frames dropped at
+    # the tie guard, frames drawn, drawn frames whose baseline failed
+    p = {"cases": np.array(tags), "table": np.array(table, np.int64), "beta_sha256": np.array(sha)}
+    for k in G16_FIELDS:
+        p[k] = np.concatenate([d[f"{t}_{k}"].ravel() for t in tags])
+    save_stable(OUT / "g16_dl_short.npz", p)
+    size = (OUT / "g16_dl_short.npz").stat().st_size
+    assert size < 1.5 * (OUT / "g7_flip.npz").stat().st_size, size
+
+
 def main():
     if len(sys.argv) > 1:
         for name in sys.argv[1:]:
@@ -402,6 +524,7 @@ def main():
     g13()
     g14()
     g15()
+    g16()
     for p in sorted(OUT.glob("*.npz")):
         print(p.name, p.stat().st_size)
 

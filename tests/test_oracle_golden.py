@@ -103,6 +103,26 @@ def test_decode_with_retries(golden):
         assert mism == 0, f"{tag}: {mism} frames differ"
 
 
+def test_decode_with_retries_short_and_odd_shapes():
+    """g16: N < 128, K = N, short CRCs, retries >= K and the N = 128 codes with K != 64, beta random
+    fp32 and None.  The generator keeps no frame whose flip choice is within 1e-9 relative of
+    another untried candidate, so every frame is held exactly (bits, success, attempts, tried)."""
+    from dl_short_cases import g16, g16_beta
+
+    g = g16()  # (g16_dl_short.npz, unpacked per case)
+    assert len(g["cases"]) == 9
+    for tag in g["cases"]:
+        info, crc, M, retries = g[f"{tag}_info"], g[f"{tag}_crc"], g[f"{tag}_M"], g[f"{tag}_retries"]
+        for name, beta in (("beta", g16_beta(tag)), ("none", None)):
+            assert g[f"{tag}_{name}_tried"].shape[1] == retries
+            for f, llr in enumerate(g[f"{tag}_llr"]):
+                r = oracle.decode_with_retries(llr, info, M, retries, crc=crc, beta=beta)
+                assert r["tried"] == [int(t) for t in g[f"{tag}_{name}_tried"][f] if t >= 0], (tag, name, f)
+                assert r["attempts"] == g[f"{tag}_{name}_attempts"][f], (tag, name, f)
+                assert r["success"] == bool(g[f"{tag}_{name}_success"][f]), (tag, name, f)
+                np.testing.assert_array_equal(r["bits"], g[f"{tag}_{name}_bits"][f], err_msg=f"{tag} {name} {f}")
+
+
 def test_batch_matches_single(golden):
     g = golden("g4_decode.npz")
     llr = g["M8_snr3_llr"]
