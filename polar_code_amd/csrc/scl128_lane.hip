@@ -120,6 +120,27 @@ __device__ __forceinline__ uint64_t flip_order_key(double q) {
 #define PSCL_LANE_WAVES_PER_EU 2
 #endif
 
+// Instruction-count trims of the plain instances (L = 8 and 4, codes 1 and 2; the FS, FP, TXF and EX
+// instances keep the forms below them).  Each is bit-neutral and can be switched off alone.
+// U0T: u0 is final after phase 63 and is read afterwards only as polar_transform64(u0) (the depth-1
+// partial sums of the recomputes at phases 64, 80, 96 and 112) and by the epilogue.  At phase 64
+// the lanes replace u0 by its transform in place -- a later pull carries the transformed word as it
+// carried u0 -- and the epilogue applies the transform once more: every stage x ^= (x >> s) & M
+// writes only bits it does not read, so it undoes itself, and the stages commute (an involution).
+#ifndef PSCL_LANE_U0T
+#define PSCL_LANE_U0T 1
+#endif
+// GSPLIT: the depth-1 g nodes of the recomputes at phases 64..112 flip the sign of a channel value
+// that must survive, so each built a new register pair: the flipped high word plus a copy of the
+// untouched low word (~0.8 v_mov per g node).  From phase 64 on the channel a-operands c[8 h + m],
+// m < 4, are read by those g nodes only, so their high words are kept a second time (ah[], +4 EPL
+// VGPRs, made opaque so they stay apart from c[]) and the g node forms its operand from c's low
+// word and the flipped copy: c's own high register is dead by then and takes the flipped word, the
+// low word stays where it is.
+#ifndef PSCL_LANE_GSPLIT
+#define PSCL_LANE_GSPLIT 1
+#endif
+
 // FS: the DL-SCL retry decodes (dlscl.hip, capi.cpp dl_retry_chunk) -- a round's entries read
 // bucket by bucket (P.elist), LLR rows by indirection (P.fidx), forced information bits (P.force:
 // the reference bits below the flip index, the flipped bit at it, scl.py:146-161) and the warm
@@ -229,6 +250,9 @@ scl_lane_kernel(const pscl_decode_params P) {
     // the margin-raised key hi(fma(m, 1 + 2^-40, MARGIN)) as one VOP3 fma with the factor in an SGPR
     // (left to itself the compiler emits a copy of the margin register plus v_fmac_f64)
     constexpr bool BITS = !FS && !EX && PSCL_LANE_BITS;
+    constexpr bool PLAIN = !FS && !EX && !TXF;  // the instances the PSCL_LANE_U0T / GSPLIT trims apply to
+    constexpr bool U0T = PLAIN && PSCL_LANE_U0T;
+    constexpr bool GSPLIT = PLAIN && PSCL_LANE_GSPLIT && (LMAX == 8 || PSCL_LANE_CREG4);
     constexpr double MARGIN = BITS ? PSCL_TAIL2_MARGIN : PSCL_TAIL_ABS_MARGIN;
     auto hiw_up = [&](double m) {
         double r;
@@ -320,6 +344,12 @@ scl_lane_kernel(const pscl_decode_params P) {
             }
         };
         load_chan();
+        uint32_t ah[4 * EPL];  // PSCL_LANE_GSPLIT: the high words of the depth-1 g nodes' a-operands
+#pragma unroll
+        for (int m = 0; m < 4 * EPL; ++m) {
+            ah[m] = GSPLIT ? hiw(c[8 * (m >> 2) + (m & 3)]) : 0u;
+            if constexpr (GSPLIT) asm volatile("" : "+v"(ah[m]));
+        }
         if constexpr (TXF) {
             // the uncoded BPSK baseline of the same payload (channel_kernel phase A: noise pairs
             // 0x40000000 + cb), counted here while the decode's registers are still free
@@ -406,7 +436,8 @@ scl_lane_kernel(const pscl_decode_params P) {
                 if constexpr (r1 || r2 || r3) {
                     uint64_t X1 = 0;
                     uint32_t X2 = 0, X3 = 0;
-                    if (r1) X1 = polar_transform64(u0);
+                    if constexpr (U0T && phi == 64) u0 = polar_transform64(u0);  // (kept transformed from here on)
+                    if (r1) X1 = U0T ? u0 : polar_transform64(u0);
                     if (r2) {
                         constexpr int lo = phi - (phi & 31) - 32;
                         X2 = polar_transform32((uint32_t)((lo >= 64 ? u1 : u0) >> (lo & 63)));
@@ -455,8 +486,10 @@ scl_lane_kernel(const pscl_decode_params P) {
                         double d1[4];
 #pragma unroll
                         for (int m = 0; m < 4; ++m)
-                            d1[m] = r1 ? g_node_bit31(c[8 * h + m], c[8 * h + m + 4], (uint32_t)(s1[m & 1] >> (32 * (m >> 1))))
-                                       : d1l[h][m];
+                            d1[m] = !r1 ? d1l[h][m]
+                                    : GSPLIT ? g_node_bit31_split(c[8 * h + m], ah[4 * h + m], c[8 * h + m + 4],
+                                                                  (uint32_t)(s1[m & 1] >> (32 * (m >> 1))))
+                                             : g_node_bit31(c[8 * h + m], c[8 * h + m + 4], (uint32_t)(s1[m & 1] >> (32 * (m >> 1))));
                         double d2[2];
 #pragma unroll
                         for (int s2 = 0; s2 < 2; ++s2)
@@ -476,6 +509,7 @@ scl_lane_kernel(const pscl_decode_params P) {
                 uint32_t xsb = 0;  // partial sums of the first rewritten node's left sibling (g node)
                 if constexpr (phi && start >= 4) {
                     constexpr int w = 1 << (kn - start), lo = phi - w;
+                    static_assert(phi <= 64 || lo >= 64, "u0 is not read bit-wise after phase 64 (PSCL_LANE_U0T)");
                     xsb = polar_transform8((uint32_t)((lo >= 64 ? u1 : u0) >> (lo & 63)) & ((1u << w) - 1u));
                 }
                 static_for<3>([&](auto DI) {
@@ -1147,6 +1181,7 @@ scl_lane_kernel(const pscl_decode_params P) {
         // ---- epilogue: candidates u[info_set], CRC syndrome, final list order certified,
         // best = first CRC pass in list order (scl.py:176-209)
         uint64_t ib0 = 0, ib1 = 0;
+        if constexpr (U0T) u0 = polar_transform64(u0);  // (back to the decided bits)
         {
             int off = 0;
 #pragma unroll

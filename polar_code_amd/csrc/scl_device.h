@@ -93,6 +93,14 @@ __device__ __forceinline__ double g_node_bit31(double a, double b, uint32_t w) {
     return b + pscl_asf64(((uint64_t)hi << 32) | (uint32_t)ab);
 }
 
+// g_node_bit31 with a's high word given apart (ahi == the high word of a): the operand is a's low
+// word beside the flipped copy, so a register pair whose high half is dead can take it in place
+__device__ __forceinline__ double g_node_bit31_split(double a, uint32_t ahi, double b, uint32_t w) {
+    uint32_t hi;
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x6c" : "=v"(hi) : "v"(w), "v"(ahi), "s"(0x80000000u));
+    return b + pscl_asf64(((uint64_t)hi << 32) | (uint32_t)pscl_asu64(a));
+}
+
 // max(-v, 0): the part of np.logaddexp(0, -v) beyond the shared tail (bit 0 pays |v| when
 // v < 0); one v_max_f64 with the negation as a source modifier (fmax would canonicalise)
 __device__ __forceinline__ double relu_neg(double v) {
