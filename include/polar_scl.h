@@ -257,6 +257,34 @@ int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
                          uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
                          int64_t* n_escalated);
 
+/*
+ * The two halves of the adaptive decode as calls of their own, for every code length the SC
+ * kernels cover.  A caller that enqueues the next batch's pscl_sc_device before this batch's
+ * pscl_escalate_device keeps the device busy across the latter's host wait.
+ *
+ * pscl_sc_device: sc_decode (polar.py:130-168) + check_crc (crc.py:40-56) on every frame of a
+ * device batch, one lane-parallel kernel on the handle's stream, no host wait.  Frame b gets
+ * d_best[b] = u[info_set], d_flags[b] = PSCL_FLAG_CRC_PASS | 0 if the CRC holds (always without a
+ * CRC, as the plain decode) else 0, d_stage[b] = 1 or 2 (d_stage may be NULL).  With d_ref the SC
+ * results' statistics are added into d_counters as pscl_decode_device adds them (the SC baseline
+ * curve).  Pending pipelined work is ordered first.
+ *   N = 32, 64, 256, 512, 1024: plain rows of N LLRs.  N = 128: plain and rate-matched rows.
+ * PSCL_EUNSUP for N < 32, and for a rate-matched handle with N != 128.
+ *
+ * pscl_escalate_device: for every frame whose d_flags lacks PSCL_FLAG_CRC_PASS, d_best / d_flags
+ * become exactly pscl_decode_device's outputs for that frame and d_stage 2; the other frames are
+ * left alone.  The hand-off of pscl_adaptive_device: the failing frames are compacted, the call
+ * waits once for their count, their rows are gathered, decoded as a dense plain batch and scattered
+ * back.  With d_ref the final outputs of all B frames are counted, and the escalated count is added
+ * into d_counters[PSCL_CNT_ESCALATED].  Any N and L pscl_decode_device accepts, rate-matched rows
+ * included.  PSCL_EINVAL without a CRC.
+ */
+int pscl_sc_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                   uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters);
+int pscl_escalate_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                         uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                         int64_t* n_escalated);
+
 /* Device scratch helpers so that non-torch callers can drive the device path. */
 /*
  * One call per SNR point (the frame loop of run_fer_sweep.py:41-191 for global frames

@@ -44,6 +44,7 @@ EXPORTS = (
     "pscl_tail_abs_scan_device", "pscl_tail2_scan_device", "pscl_set_tuning", "pscl_timing_read_split", "pscl_decode_cpu",
     "pscl_host_stats", "pscl_path_stats",
     "pscl_simulate_device", "pscl_adaptive_device", "pscl_decode_adaptive_cpu",
+    "pscl_sc_device", "pscl_escalate_device",
 )
 
 # pscl_set_tuning knobs (include/polar_scl.h)
@@ -113,6 +114,8 @@ def lib() -> C.CDLL:
         "pscl_decode_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, C.c_int, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, C.c_int]),
         "pscl_adaptive_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, P(_i64)]),
+        "pscl_sc_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+        "pscl_escalate_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, P(_i64)]),
         "pscl_decode_adaptive_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, C.c_int, _u64, _vp, _i64, _vp, _vp, _vp, _vp,
                                                C.c_int]),
         "pscl_timing_read_split": (C.c_int, [_vp, P(_i64), P(_dbl), P(_i64), P(_dbl)]),
@@ -332,6 +335,60 @@ class Decoder:
         bits = ((words[:, j >> 6] >> (j & 63).astype(np.uint64)) & np.uint64(1)).astype(np.int8)
         return {"best_bits": bits, "crc_pass": (flags & PSCL_FLAG_CRC_PASS) != 0,
                 "best_idx": (flags & PSCL_FLAG_IDX_MASK).astype(np.int32), "stage": stage.copy(), "n_escalated": n}
+
+    def sc_device(self, d_llr: int, B: int, *, d_best: int, d_flags: int, d_stage=0, d_ref=0, k_payload=0,
+                  d_counters=0) -> None:
+        """sc_decode + check_crc on every frame of a device batch, enqueued without a host wait
+        (pscl_sc_device; N = 32 .. 1024, rate-matched rows at N = 128 only)."""
+        with self._lock:
+            check(lib().pscl_sc_device(self._h, d_llr, int(B), d_best, d_flags, d_stage or None, d_ref or None,
+                                       int(k_payload), d_counters or None))
+
+    def escalate_device(self, d_llr: int, B: int, *, d_best: int, d_flags: int, d_stage=0, d_ref=0, k_payload=0,
+                        d_counters=0) -> int:
+        """The list decode of the frames whose d_flags lack the CRC-pass bit, in place
+        (pscl_escalate_device; a CRC required).  Returns the escalated count."""
+        n = _i64()
+        with self._lock:
+            check(lib().pscl_escalate_device(self._h, d_llr, int(B), d_best, d_flags, d_stage or None, d_ref or None,
+                                             int(k_payload), d_counters or None, C.byref(n)))
+        return int(n.value)
+
+    def _staged_host(self, llr: np.ndarray, escalate: bool) -> dict:
+        llr = np.ascontiguousarray(llr, dtype=np.float64)
+        if llr.ndim == 1:
+            llr = llr[None, :]
+        B = llr.shape[0]
+        if llr.shape[1] != (self.E or self.N):
+            raise ValueError("Channel LLR length must be a power of two" if not self.E
+                             else f"expected {self.E} rate-matched LLRs per frame")
+        n = 0
+        with DeviceArena(self) as mem:
+            d_llr = mem.alloc(max(llr.nbytes, 8))
+            d_best = mem.alloc(max(B * self.W * 8, 8))
+            d_flags = mem.alloc(max(B, 8))
+            d_stage = mem.alloc(max(B, 8))
+            if B:
+                mem.upload(d_llr, llr)
+            self.sc_device(d_llr, B, d_best=d_best, d_flags=d_flags, d_stage=d_stage)
+            if escalate:
+                n = self.escalate_device(d_llr, B, d_best=d_best, d_flags=d_flags, d_stage=d_stage)
+            words = mem.download(d_best, max(B * self.W * 8, 8), np.uint64)[:B * self.W].reshape(B, self.W)
+            flags = mem.download(d_flags, max(B, 8), np.uint8)[:B]
+            stage = mem.download(d_stage, max(B, 8), np.uint8)[:B]
+        j = np.arange(self.K)
+        bits = ((words[:, j >> 6] >> (j & 63).astype(np.uint64)) & np.uint64(1)).astype(np.int8)
+        return {"best_bits": bits, "crc_pass": (flags & PSCL_FLAG_CRC_PASS) != 0,
+                "best_idx": (flags & PSCL_FLAG_IDX_MASK).astype(np.int32), "stage": stage.copy(), "n_escalated": n}
+
+    def decode_sc(self, llr: np.ndarray):
+        """Host form of sc_device: llr [B, N] float64 -> (best_bits [B, K] int8, crc_pass [B] bool)."""
+        out = self._staged_host(llr, escalate=False)
+        return out["best_bits"], out["crc_pass"]
+
+    def decode_staged(self, llr: np.ndarray) -> dict:
+        """sc_device then escalate_device on host rows: decode_adaptive's dict, at any N >= 32."""
+        return self._staged_host(llr, escalate=True)
 
     def channel_device(self, seed: int, stream_id: int, ebno_db: float, rate: float, k_payload: int, frame0: int,
                        B: int, d_llr: int, d_msg: int = 0) -> None:

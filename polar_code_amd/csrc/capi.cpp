@@ -820,52 +820,12 @@ int pscl_decode_device(pscl_handle* h, const double* d_llr, int64_t B, const uin
     return launch_decode(h, P, hist, nullptr, 38, h->pipelined);
 }
 
-// Adaptive decode (include/polar_scl.h): stage 1 is the lane-parallel SC kernel over all B frames;
-// the frames whose SC result fails the CRC are compacted (dl_compact on the flags), their rows
-// gathered densely into scratch, decoded by launch_decode as a plain decode of that many frames --
-// the screening path, not a row list, which would land on the exact kernel -- and scattered back.
-// Scratch slots 72..76: count, frame list, dense rows, dense best words, dense flags.  One host
-// wait, after stage 1: the escalated count sizes the dense batch.
-int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
-                         uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
-                         int64_t* n_escalated) {
-    if (!h) return fail(PSCL_EINVAL, "NULL handle");
-    if (n_escalated) *n_escalated = 0;
-    if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
-    if (!h->crc_poly) return fail(PSCL_EINVAL, "adaptive decoding needs a CRC (without one every SC result passes)");
-    if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
-    if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
-    if (h->N != PSCL_FAST_N)
-        return fail(PSCL_EUNSUP, "adaptive decoding is implemented for N = %d only (N = %d)", PSCL_FAST_N, h->N);
-    if (B == 0) return PSCL_OK;
-    if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
-    if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
-    int rc = enter(h);  // (pending pipelined work first; the call runs stream-ordered)
-    if (rc) return rc;
-    const int W = h->W;
-    const int64_t row = h->rm_E ? h->rm_E : h->N;
+namespace {
+
+// the SC stage over all B frames as one launch on the handle's stream (sc128_lane.hip at N = 128,
+// sc_lane.hip at the other lengths), timed like a decode when timing is on
+int launch_sc_stage(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags, uint8_t* d_stage) {
     hipStream_t s = h->stream;
-    hipError_t e;
-    if (!h->h_adapt) HIP_TRY(hipHostMalloc((void**)&h->h_adapt, 4, hipHostMallocDefault));
-    void *d_cnt, *d_act;
-    if ((rc = ensure(h, 72, 4, &d_cnt))) return rc;
-    if ((rc = ensure(h, 73, (size_t)B * 8, &d_act))) return rc;
-    // stage 1
-    pscl_sc_params S;
-    memset(&S, 0, sizeof(S));
-    S.llr = d_llr;
-    S.B = B;
-    S.K = h->K;
-    S.W = W;
-    S.info_mask[0] = h->info_mask[0];
-    S.info_mask[1] = h->info_mask[1];
-    S.epi_table = h->d_epi;
-    S.epi_words = h->epi_words;
-    S.rm_E = h->rm_E;
-    S.rm_src = h->d_rm_src;
-    S.best = d_best;
-    S.flags = d_flags;
-    S.stage = d_stage;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->timing) {  // (the SC launch is one timed launch on the handle's stream, like a decode)
         while (h->ev_pool.size() < h->ev_used + 2) {
@@ -880,9 +840,63 @@ int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
         h->ev_used += 2;
         HIP_TRY(hipEventRecord(e0, s));
     }
-    if ((e = pscl_launch_sc_lane(S, s)) != hipSuccess) return fail(PSCL_EDEVICE, "sc kernel launch: %s", hipGetErrorString(e));
+    hipError_t e;
+    if (h->N == PSCL_FAST_N) {
+        pscl_sc_params S;
+        memset(&S, 0, sizeof(S));
+        S.llr = d_llr;
+        S.B = B;
+        S.K = h->K;
+        S.W = h->W;
+        S.info_mask[0] = h->info_mask[0];
+        S.info_mask[1] = h->info_mask[1];
+        S.epi_table = h->d_epi;
+        S.epi_words = h->epi_words;
+        S.rm_E = h->rm_E;
+        S.rm_src = h->d_rm_src;
+        S.best = d_best;
+        S.flags = d_flags;
+        S.stage = d_stage;
+        e = pscl_launch_sc_lane(S, s);
+    } else {
+        if (!pscl_scn_lane_available(h->N) || h->rm_E)
+            return fail(PSCL_EUNSUP, "no SC kernel for N = %d%s", h->N, h->rm_E ? " with rate matching" : "");
+        pscl_scn_params S;
+        memset(&S, 0, sizeof(S));
+        S.llr = d_llr;
+        S.B = B;
+        S.N = h->N;
+        S.K = h->K;
+        S.W = h->W;
+        for (size_t k = 0; k < h->info_words.size() && k < 16; ++k) S.info_mask[k] = h->info_words[k];
+        S.epi_table = h->d_epi;
+        S.epi_words = h->epi_words;
+        S.best = d_best;
+        S.flags = d_flags;
+        S.stage = d_stage;
+        e = pscl_launch_scn_lane(S, s);
+    }
+    if (e != hipSuccess) return fail(PSCL_EDEVICE, "sc kernel launch: %s", hipGetErrorString(e));
     if (h->timing) HIP_TRY(hipEventRecord(e1, s));
-    // the failing frames and their count
+    return PSCL_OK;
+}
+
+// the hand-off to the list decoder: the frames whose flags lack PSCL_FLAG_CRC_PASS are compacted
+// (dl_compact), their rows gathered densely into scratch, decoded by launch_decode as a plain decode
+// of that many frames -- the screening path, not a row list, which would land on the exact kernel --
+// and scattered back; d_stage (or null) gets 2 at those frames.  Scratch slots 72..76: count, frame
+// list, dense rows, dense best words, dense flags.  One host wait: the count sizes the dense batch.
+int escalate_failed(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags, uint8_t* d_stage,
+                    int64_t* n_out) {
+    const int W = h->W;
+    const int64_t row = h->rm_E ? h->rm_E : h->N;
+    hipStream_t s = h->stream;
+    hipError_t e;
+    int rc;
+    if (!h->h_adapt) HIP_TRY(hipHostMalloc((void**)&h->h_adapt, 4, hipHostMallocDefault));
+    void *d_cnt, *d_act;
+    if ((rc = ensure(h, 72, 4, &d_cnt))) return rc;
+    if ((rc = ensure(h, 73, (size_t)B * 8, &d_act))) return rc;
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 4, s));
     if ((e = pscl_launch_dl_compact(d_flags, B, 0, (int64_t*)d_act, nullptr, (int32_t*)d_cnt, s)) != hipSuccess)
         return fail(PSCL_EDEVICE, "dl_compact launch: %s", hipGetErrorString(e));
@@ -890,7 +904,7 @@ int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
     HIP_TRY(hipStreamSynchronize(s));  // the call's one host wait
     const int64_t n = *h->h_adapt;
     if (n < 0 || n > B) return fail(PSCL_EDEVICE, "escalated count %lld out of range", (long long)n);
-    if (n_escalated) *n_escalated = n;
+    *n_out = n;
     if (n > 0) {
         // stage 2: a plain decode of the dense batch
         void *d_rows, *d_b2, *d_f2;
@@ -910,14 +924,87 @@ int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
         if ((e = pscl_launch_scatter_results((const int64_t*)d_act, n, W, (const uint64_t*)d_b2, (const uint8_t*)d_f2, d_best,
                                              d_flags, s)) != hipSuccess)
             return fail(PSCL_EDEVICE, "scatter launch: %s", hipGetErrorString(e));
-    }
-    if (d_ref) {  // statistics of the final outputs, as a plain decode adds them, and the escalated count
-        if ((e = pscl_launch_dl_count(d_best, d_flags, d_ref, B, W, k_payload, d_counters, s)) != hipSuccess)
-            return fail(PSCL_EDEVICE, "dl_count launch: %s", hipGetErrorString(e));
-        if (n > 0 && (e = pscl_launch_add_counter(d_counters, PSCL_CNT_ESCALATED, n, s)) != hipSuccess)
-            return fail(PSCL_EDEVICE, "counter launch: %s", hipGetErrorString(e));
+        if (d_stage && (e = pscl_launch_mark_stage((const int64_t*)d_act, n, d_stage, s)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "stage launch: %s", hipGetErrorString(e));
     }
     return PSCL_OK;
+}
+
+// statistics of the outputs of all B frames, as a plain decode adds them, and the escalated count
+int count_final(pscl_handle* h, const uint64_t* d_best, const uint8_t* d_flags, int64_t B, const uint64_t* d_ref,
+                int k_payload, int64_t* d_counters, int64_t n_escalated) {
+    if (!d_ref) return PSCL_OK;
+    hipError_t e;
+    if ((e = pscl_launch_dl_count(d_best, d_flags, d_ref, B, h->W, k_payload, d_counters, h->stream)) != hipSuccess)
+        return fail(PSCL_EDEVICE, "dl_count launch: %s", hipGetErrorString(e));
+    if (n_escalated > 0 &&
+        (e = pscl_launch_add_counter(d_counters, PSCL_CNT_ESCALATED, n_escalated, h->stream)) != hipSuccess)
+        return fail(PSCL_EDEVICE, "counter launch: %s", hipGetErrorString(e));
+    return PSCL_OK;
+}
+
+}  // namespace
+
+// Adaptive decode (include/polar_scl.h): stage 1 is the lane-parallel SC kernel over all B frames
+// (launch_sc_stage), stage 2 the hand-off of the frames that fail the CRC (escalate_failed).
+int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                         uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                         int64_t* n_escalated) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (n_escalated) *n_escalated = 0;
+    if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
+    if (!h->crc_poly) return fail(PSCL_EINVAL, "adaptive decoding needs a CRC (without one every SC result passes)");
+    if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
+    if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
+    if (h->N != PSCL_FAST_N)
+        return fail(PSCL_EUNSUP, "adaptive decoding is implemented for N = %d only (N = %d)", PSCL_FAST_N, h->N);
+    if (B == 0) return PSCL_OK;
+    if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
+    if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
+    int rc = enter(h);  // (pending pipelined work first; the call runs stream-ordered)
+    if (rc) return rc;
+    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage))) return rc;
+    int64_t n = 0;
+    if ((rc = escalate_failed(h, d_llr, B, d_best, d_flags, nullptr, &n))) return rc;  // (stage 1 wrote the stages)
+    if (n_escalated) *n_escalated = n;
+    return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, n);
+}
+
+int pscl_sc_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                   uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
+    if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
+    if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
+    if (h->N < 32) return fail(PSCL_EUNSUP, "the SC stage is implemented for N = 32 .. %d (N = %d)", PSCL_MAX_N, h->N);
+    if (h->rm_E && h->N != PSCL_FAST_N)
+        return fail(PSCL_EUNSUP, "the SC stage takes rate-matched rows at N = %d only (N = %d)", PSCL_FAST_N, h->N);
+    if (B == 0) return PSCL_OK;
+    if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
+    int rc = enter(h);  // (pending pipelined work first)
+    if (rc) return rc;
+    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage))) return rc;
+    return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, 0);
+}
+
+int pscl_escalate_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                         uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                         int64_t* n_escalated) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (n_escalated) *n_escalated = 0;
+    if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
+    if (!h->crc_poly) return fail(PSCL_EINVAL, "escalation needs a CRC (without one every SC result passes)");
+    if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
+    if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
+    if (B == 0) return PSCL_OK;
+    if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
+    if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
+    int rc = enter(h);
+    if (rc) return rc;
+    int64_t n = 0;
+    if ((rc = escalate_failed(h, d_llr, B, d_best, d_flags, d_stage, &n))) return rc;
+    if (n_escalated) *n_escalated = n;
+    return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, n);
 }
 
 int pscl_join(pscl_handle* h) {

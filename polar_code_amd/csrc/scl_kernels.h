@@ -274,6 +274,27 @@ hipError_t pscl_launch_scatter_results(const int64_t* act, int64_t n, int W, con
                                        const uint8_t* flags_in, uint64_t* best, uint8_t* flags, hipStream_t s);
 hipError_t pscl_launch_add_counter(int64_t* counters, int slot, int64_t v, hipStream_t s);
 
+// Lane-parallel successive cancellation of the other code lengths (sc_lane.hip, N = 32, 64, 256,
+// 512, 1024; plain rows only): pscl_sc_device.  Outputs as pscl_sc_params'.
+struct pscl_scn_params {
+    const double* llr;           // [B][N]
+    int64_t B;
+    int N, K, W;
+    uint64_t info_mask[16];      // bit phi of word phi / 64 set <=> phase phi is an information bit
+    const uint64_t* epi_table;   // the handle's epilogue tables: u-byte gather [max(N / 8, 16)][256]
+                                 // uint8, then information nibble -> CRC syndrome [K4][16] uint32
+    int epi_words;
+    uint64_t* best;              // [B][W]
+    uint8_t* flags;              // [B]
+    uint8_t* stage;              // [B] or null
+};
+int pscl_scn_lane_available(int N);
+int pscl_scn_lane_lds(const pscl_scn_params& P);
+int64_t pscl_scn_lane_grid(const pscl_scn_params& P);
+hipError_t pscl_launch_scn_lane(const pscl_scn_params& P, hipStream_t s);
+// stage[act[i]] = 2, i < n (the frames pscl_escalate_device hands to the list decoder)
+hipError_t pscl_launch_mark_stage(const int64_t* act, int64_t n, uint8_t* stage, hipStream_t s);
+
 int pscl_decode_lmax(int L);
 // scl_long.hip (N = 256 .. 1024)
 int64_t pscl_long_block_bytes(int N, int L, int K, int hist);

@@ -144,5 +144,38 @@ class SCLDecoder:
             d_counters=counters.data_ptr() if counters is not None else 0)
         return best, flags, stage
 
+    def decode_sc(self, llr: np.ndarray):
+        """sc_decode + check_crc on every frame (pscl_sc_device, N = 32 .. 1024): (bits [B, K] int8,
+        crc_pass [B] bool)."""
+        return self._dec.decode_sc(llr)
+
+    def decode_staged(self, llr: np.ndarray) -> dict:
+        """decode_adaptive's result at any N >= 32, as the SC stage followed by the escalation
+        (pscl_sc_device, pscl_escalate_device)."""
+        out = self._dec.decode_staged(llr)
+        out["bits"] = out.pop("best_bits")
+        return out
+
+    def decode_tensor_staged(self, llr, ref_words=None, k_payload: int = 0, counters=None):
+        """Device path of decode_staged on the caller's current torch stream: returns
+        decode_tensor_adaptive's tensors.  The call waits once on the host, inside the escalation."""
+        import torch
+
+        row = self._dec.E or self.N
+        if llr.dtype != torch.float64 or not llr.is_contiguous() or llr.dim() != 2 or llr.shape[1] != row:
+            raise ValueError("llr must be a contiguous float64 [B, N] tensor")
+        B = llr.shape[0]
+        W = self._dec.W
+        best = torch.empty((B, W), dtype=torch.int64, device=llr.device)
+        flags = torch.empty((B,), dtype=torch.uint8, device=llr.device)
+        stage = torch.empty((B,), dtype=torch.uint8, device=llr.device)
+        self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
+        out = dict(d_best=best.data_ptr(), d_flags=flags.data_ptr(), d_stage=stage.data_ptr())
+        self._dec.sc_device(llr.data_ptr(), B, **out)
+        self._dec.escalate_device(
+            llr.data_ptr(), B, **out, d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
+            d_counters=counters.data_ptr() if counters is not None else 0)
+        return best, flags, stage
+
 
 __all__ = ["decode_scl", "SCLDecoder"]
