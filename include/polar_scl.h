@@ -285,6 +285,61 @@ int pscl_escalate_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
                          uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
                          int64_t* n_escalated);
 
+/*
+ * The adaptive decode without the host wait.  Per frame the results are pscl_adaptive_device's
+ * (N = 128) and pscl_sc_device followed by pscl_escalate_device's (the other lengths): the
+ * composition of sc_decode + check_crc and decode_scl, bit for bit.  Coverage is pscl_sc_device's:
+ * N = 32 .. 1024 plain rows, N = 128 rate-matched rows too.
+ * Everything is enqueued and the call returns: the SC stage over all B frames; the compaction of
+ * the failing frames into a row list and a count in handle scratch; the list decode of "the first
+ * count rows of the list, results at their rows", sized on the device -- the row-list screening
+ * decode (N = 128 .. 1024, L = 4 .. 32) plus the exact re-decode of the frames it defers, or, where
+ * the handle's plain decode is exact (L <= 2, N < 128, screening off), the exact kernel on the same
+ * list; with d_ref the statistics of the final outputs of all B frames.  d_stage needs no marking:
+ * the SC kernel writes 1 or 2.
+ *   d_n_escalated  NULL or a device int32: receives the escalated count
+ *   d_counters     with d_ref: the final outputs' statistics are added as pscl_decode_device adds
+ *                  them, and the escalated count into d_counters[PSCL_CNT_ESCALATED]
+ * Consecutive calls reuse the scratch in stream order.  On a pipelined handle
+ * (pscl_set_pipelined >= 1) the SC stage and the compaction stay on the handle's stream, and the
+ * rest -- list decode, re-decode, statistics, escalated count -- goes to one of two side streams,
+ * where it overlaps the next call's SC stage and the previous call's rest; list and count scratch
+ * and the side streams alternate two parities.  The
+ * call's input, output and counter buffers then stay in use until pscl_join, pscl_sync, any other
+ * entry point on the handle, or the second following pipelined call; consecutive pipelined calls
+ * must not write the same output buffers.  Results are bit-identical to the non-pipelined form.
+ * PSCL_EINVAL without a CRC, for B < 0, for d_ref without d_counters and for a missing d_llr /
+ * d_best / d_flags; PSCL_EUNSUP for N < 32, rate matching at N != 128 and B > 2^31 - 1.
+ */
+int pscl_adaptive_async_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                               uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                               int32_t* d_n_escalated);
+
+/*
+ * One SNR point of a Monte-Carlo sweep with adaptive decoding, for global frames
+ * [frame0, frame0 + B): pscl_channel_device (and the optional uncoded baseline) with the Philox
+ * stream pscl_simulate uses -- shards add up exactly -- then the SC stage and the escalation of
+ * pscl_adaptive_async_device, over chunks of up to 2^20 frames in handle scratch.  Counters are
+ * ADDED into int64 [3][PSCL_NCOUNT]: row 0 the SC results of every frame (the SC baseline curve),
+ * row 1 the final adaptive outputs with PSCL_CNT_ESCALATED, row 2 uncoded (include_uncoded).
+ * The device form makes no host wait: stream-ordered on the handle's stream, d_counters zeroed by
+ * the caller and complete once the stream has run.  The host form zeroes, enqueues, waits and
+ * copies back.  Errors as pscl_adaptive_async_device's and pscl_channel_device's.
+ */
+int pscl_simulate_adaptive_device(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate,
+                                  int k_payload, int64_t frame0, int64_t B, int include_uncoded, int64_t* d_counters);
+int pscl_simulate_adaptive(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate,
+                           int k_payload, int64_t frame0, int64_t B, int include_uncoded, int64_t* counters);
+
+/*
+ * Which path pscl_adaptive_async_device / pscl_simulate_adaptive[_device] took since the handle was
+ * created (or the last reset = 1): stage-2 launches on a row-list screening kernel, stage-2
+ * launches on an exact kernel, and the number of times those entry points blocked the host (a
+ * scratch buffer that had to grow while side-stream work was pending; 0 after a warm-up call of
+ * the same B).  Any output pointer may be NULL.
+ */
+int pscl_adaptive_stats(pscl_handle* h, int64_t* screened, int64_t* exact, int64_t* host_waits, int reset);
+
 /* Device scratch helpers so that non-torch callers can drive the device path. */
 /*
  * One call per SNR point (the frame loop of run_fer_sweep.py:41-191 for global frames
@@ -407,6 +462,10 @@ int pscl_join(pscl_handle* h);
  *   PSCL_TUNE_DL_TAIL       1: a pipelined DL-SCL call's baseline tail (the re-decode of its deferred
  *                           frames, the compaction of the failing ones) on the handle's stream, before
  *                           the next call's baseline; 0 (default): on a stream of its own beside it
+ *   PSCL_TUNE_ADAPT_GRID    1..2^20: workgroup cap of pscl_adaptive_async_device's row-list launch
+ *                           (its workgroups then stride over the list); 0 (default): a grid sized
+ *                           for B, whose workgroups past the count exit at once -- the measured
+ *                           faster
  */
 #define PSCL_TUNE_DL_SCREEN 1
 #define PSCL_TUNE_DL_CHUNKS 2
@@ -425,7 +484,8 @@ int pscl_join(pscl_handle* h);
 #define PSCL_TUNE_LANE_EXACT 15
 #define PSCL_TUNE_DL_WARM_APX 16
 #define PSCL_TUNE_DL_TAIL 17
-#define PSCL_TUNE_COUNT 18
+#define PSCL_TUNE_ADAPT_GRID 18
+#define PSCL_TUNE_COUNT 19
 int pscl_set_tuning(pscl_handle* h, int knob, int64_t value);
 
 /*

@@ -45,11 +45,12 @@ EXPORTS = (
     "pscl_host_stats", "pscl_path_stats",
     "pscl_simulate_device", "pscl_adaptive_device", "pscl_decode_adaptive_cpu",
     "pscl_sc_device", "pscl_escalate_device",
+    "pscl_adaptive_async_device", "pscl_simulate_adaptive", "pscl_simulate_adaptive_device", "pscl_adaptive_stats",
 )
 
 # pscl_set_tuning knobs (include/polar_scl.h)
 TUNE = {"dl_screen": 1, "dl_chunks": 2, "dl_split": 3, "side_priority": 4, "post_grid": 5, "retry_wpg": 6, "dl_lane": 7, "dl_screen_min": 8, "dl_retry_lane": 9, "post_pairs": 10, "dl_streams": 11, "tx_fused": 12,
-        "dl_fused_post": 13, "post_epw": 14, "lane_exact": 15, "dl_warm_apx": 16, "dl_tail": 17}
+        "dl_fused_post": 13, "post_epw": 14, "lane_exact": 15, "dl_warm_apx": 16, "dl_tail": 17, "adapt_grid": 18}
 
 _vp, _i32, _i64, _u64, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
 
@@ -118,6 +119,10 @@ def lib() -> C.CDLL:
         "pscl_escalate_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, P(_i64)]),
         "pscl_decode_adaptive_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, C.c_int, _u64, _vp, _i64, _vp, _vp, _vp, _vp,
                                                C.c_int]),
+        "pscl_adaptive_async_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+        "pscl_simulate_adaptive_device": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, _vp]),
+        "pscl_simulate_adaptive": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, _vp]),
+        "pscl_adaptive_stats": (C.c_int, [_vp, P(_i64), P(_i64), P(_i64), C.c_int]),
         "pscl_timing_read_split": (C.c_int, [_vp, P(_i64), P(_dbl), P(_i64), P(_dbl)]),
         "pscl_host_stats": (C.c_int, [_vp, P(_dbl), P(_dbl), P(_i64), C.c_int]),
         "pscl_path_stats": (C.c_int, [_vp, P(_i64), P(_i64), P(_i64), P(_i64), P(_i64)]),
@@ -354,6 +359,24 @@ class Decoder:
                                              int(k_payload), d_counters or None, C.byref(n)))
         return int(n.value)
 
+    def adaptive_async_device(self, d_llr: int, B: int, *, d_best: int, d_flags: int, d_stage=0, d_ref=0, k_payload=0,
+                              d_counters=0, d_n_escalated=0) -> None:
+        """The adaptive decode enqueued without a host wait (pscl_adaptive_async_device; N = 32 ..
+        1024, a CRC required): SC, the compaction of the failing frames, the list decode of the
+        listed rows, the statistics.  d_n_escalated: a device int32 that receives the escalated
+        count.  On a pipelined handle stage 2 runs on the side stream (join() / sync() order it back)."""
+        with self._lock:
+            check(lib().pscl_adaptive_async_device(self._h, d_llr or None, int(B), d_best or None, d_flags or None,
+                                                   d_stage or None, d_ref or None, int(k_payload), d_counters or None,
+                                                   d_n_escalated or None))
+
+    def adaptive_stats(self, reset: bool = False) -> dict:
+        """Paths of the adaptive calls without a host wait (pscl_adaptive_stats): stage-2 launches on
+        a row-list screening kernel, on an exact kernel, and the times a call blocked the host."""
+        a, b, c = _i64(), _i64(), _i64()
+        check(lib().pscl_adaptive_stats(self._h, C.byref(a), C.byref(b), C.byref(c), 1 if reset else 0))
+        return {"screened": int(a.value), "exact": int(b.value), "host_waits": int(c.value)}
+
     def _staged_host(self, llr: np.ndarray, escalate: bool) -> dict:
         llr = np.ascontiguousarray(llr, dtype=np.float64)
         if llr.ndim == 1:
@@ -473,6 +496,26 @@ class Decoder:
             check(lib().pscl_simulate_device(self._h, int(seed) & (2**64 - 1), int(stream_id) & 0xFFFFFFFF,
                                              float(ebno_db), float(rate), int(k_payload), int(frame0), int(B),
                                              int(retries), int(bool(include_uncoded)), d_counters))
+
+    def simulate_adaptive(self, seed: int, stream_id: int, ebno_db: float, rate: float, k_payload: int, frame0: int,
+                          B: int, include_uncoded: bool = False) -> np.ndarray:
+        """One SNR point with adaptive decoding in one call (pscl_simulate_adaptive): int64 counters
+        [3, PSCL_NCOUNT], rows SC, adaptive (with CNT_ESCALATED), uncoded."""
+        out = np.zeros((3, PSCL_NCOUNT), np.int64)
+        with self._lock:
+            check(lib().pscl_simulate_adaptive(self._h, int(seed) & (2**64 - 1), int(stream_id) & 0xFFFFFFFF,
+                                               float(ebno_db), float(rate), int(k_payload), int(frame0), int(B),
+                                               int(bool(include_uncoded)), out.ctypes.data))
+        return out
+
+    def simulate_adaptive_device(self, seed: int, stream_id: int, ebno_db: float, rate: float, k_payload: int,
+                                 frame0: int, B: int, include_uncoded: bool, d_counters: int) -> None:
+        """pscl_simulate_adaptive enqueued without a host wait, counters ADDED into device int64
+        [3, PSCL_NCOUNT] at d_counters (complete after sync())."""
+        with self._lock:
+            check(lib().pscl_simulate_adaptive_device(self._h, int(seed) & (2**64 - 1), int(stream_id) & 0xFFFFFFFF,
+                                                      float(ebno_db), float(rate), int(k_payload), int(frame0), int(B),
+                                                      int(bool(include_uncoded)), d_counters or None))
 
     def screening_count(self) -> int:
         """Frames the last screening decode handed to the exact re-decode (synchronizes)."""

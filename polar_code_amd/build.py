@@ -23,7 +23,7 @@ LIB = PKG / "libpolar_mi355x.so"
 ARCH = os.environ.get("PSCL_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["scl_kernels.hip", "scl128.hip", "scl128_spec.hip", "scl128_lane.hip", "sc128_lane.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "capi.cpp",
+HIP_SOURCES = ["scl_kernels.hip", "scl128.hip", "scl128_spec.hip", "scl128_lane.hip", "scl128_lane_rl.hip", "sc128_lane.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "capi.cpp",
                "scl_cpu.cpp"]
 HIP_DEPS = HIP_SOURCES + ["scl_kernels.h", "scl_device.h", "scl128_impl.h", "glibc_softplus.h", "exp_table.inc"]
 # scl128_spec.hip is compiled once per (information-set code, list size): 8 objects
@@ -105,6 +105,8 @@ def unit_key(unit, flags: list[str]) -> str:
     h = hashlib.sha256()
     h.update("\0".join([ARCH, HIPCC, *BASE_FLAGS, *unit[1], *flags]).encode())
     headers = sorted([*CSRC.glob("*.h"), *CSRC.glob("*.inc"), *INCLUDE.glob("*.h")])
+    if unit[0].name == "scl128_lane_rl.hip":  # (it compiles scl128_lane.hip with another switch)
+        headers.append(CSRC / "scl128_lane.hip")
     for f in [unit[0], *headers]:
         h.update(f.name.encode() + b"\0" + f.read_bytes())
     return h.hexdigest()[:32]

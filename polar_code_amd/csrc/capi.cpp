@@ -134,7 +134,7 @@ struct pscl_handle {
     int rm_E = 0;                     // NR rate matching (0 = off)
     int32_t* d_rm_src = nullptr;      // [N] de-interleave gather index
     int32_t* d_rm_order = nullptr;    // [N] interleaver order
-    DevBuf scratch[128];
+    DevBuf scratch[160];
     hipStream_t retry_stream[kChainStreams] = {};  // DL-SCL retry chains: [2 set + k], chain k of a call
     hipStream_t side_stream[kChainStreams] = {};   // their deferred-entry work (PSCL_TUNE_DL_SCREEN)
     // the side streams of the other pipelining mode (their priority differs, create_priority_stream),
@@ -193,6 +193,17 @@ struct pscl_handle {
     double host_call_ms = 0.0, host_wait_ms = 0.0;  // pscl_host_stats
     int64_t host_calls = 0;
     int64_t n_fpost_rounds = 0, n_post_rounds = 0, n_fused_tx = 0, n_post_epw4 = 0, n_lane_exact = 0;  // pscl_path_stats
+    // pscl_adaptive_async_device on a pipelined handle: stage 2 (the row-list decode, its re-decode, the
+    // statistics) runs on a side stream behind ev_adc[q] and overlaps the next call's SC stage; list
+    // and count scratch alternate two parities (slots kAdSlot[q] ..), and so do the side streams
+    // (parity 0 pipe_stream, parity 1 ad_stream): the latency-bound re-decode tails of consecutive
+    // calls run beside each other, as on two handles.  ev_ad[q] marks the end of parity q's stage 2
+    hipStream_t ad_stream = nullptr;
+    hipEvent_t ev_adc[2] = {nullptr, nullptr}, ev_ad[2] = {nullptr, nullptr};
+    bool ad_pending[2] = {false, false};
+    int ad_par = 0;
+    int64_t n_regrow = 0;  // scratch buffers freed and regrown (each drains the side streams on the host)
+    int64_t n_ad_screened = 0, n_ad_exact = 0, n_ad_waits = 0;  // pscl_adaptive_stats
 };
 
 namespace {
@@ -205,6 +216,7 @@ int ensure(pscl_handle* h, int slot, size_t bytes, void** out) {
         if (b.p) {
             quiesce(h);  // (pipelined work may still read it)
             hipFree(b.p);
+            h->n_regrow++;
         }
         b.p = nullptr;
         b.n = 0;
@@ -223,7 +235,8 @@ int set_device(pscl_handle* h) {
 }
 
 // the handle's stream waits for the pending pipelined work (no host wait): what = 1 the plain
-// decodes' re-decodes, 2 the DL-SCL retry chains, 3 both
+// decodes' re-decodes and the adaptive calls' second stages, 2 the DL-SCL retry chains, 3 both;
+// + 8: not the adaptive calls' (a pipelined pscl_adaptive_async_device orders those by parity)
 int dl_enqueue_deferred(pscl_handle* h, bool beside = false);
 
 int join_pipe(pscl_handle* h, int what = 3) {
@@ -235,6 +248,11 @@ int join_pipe(pscl_handle* h, int what = 3) {
         if ((what & 2) && h->tail_pending[p]) {
             HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_tail[p], 0));
             h->tail_pending[p] = false;
+        }
+    for (int p = 0; p < 2; ++p)
+        if ((what & 1) && !(what & 8) && h->ad_pending[p]) {
+            HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_ad[p], 0));
+            h->ad_pending[p] = false;
         }
     for (int p = 0; p < kDlPar; ++p) {
         if ((what & 1) && p < 2 && h->px_pending[p]) {
@@ -254,6 +272,7 @@ int join_pipe(pscl_handle* h, int what = 3) {
 void quiesce(pscl_handle* h) {
     if (h->pipe_stream) hipStreamSynchronize(h->pipe_stream);
     if (h->tail_stream) hipStreamSynchronize(h->tail_stream);
+    if (h->ad_stream) hipStreamSynchronize(h->ad_stream);
     for (int i = 0; i < kChainStreams; ++i) {
         if (h->retry_stream[i]) hipStreamSynchronize(h->retry_stream[i]);
         if (h->side_stream[i]) hipStreamSynchronize(h->side_stream[i]);
@@ -275,6 +294,8 @@ void drop_side_streams(pscl_handle* h) {
     h->pipe_stream = nullptr;
     if (h->tail_stream) hipStreamDestroy(h->tail_stream);
     h->tail_stream = nullptr;
+    if (h->ad_stream) hipStreamDestroy(h->ad_stream);
+    h->ad_stream = nullptr;
     for (int i = 0; i < kChainStreams; ++i) {
         if (h->retry_stream[i]) hipStreamDestroy(h->retry_stream[i]);
         if (h->side_stream[i]) hipStreamDestroy(h->side_stream[i]);
@@ -412,8 +433,8 @@ int launch_decode(pscl_handle* h, const pscl_decode_params& P0, int hist, hipStr
             h->tail_pending[tail_par] = false;
         }
         if (pipe) {
-            if (!h->pipe_stream) {
-                HIP_TRY(create_priority_stream(h, &h->pipe_stream));
+            if (!h->pipe_stream) HIP_TRY(create_priority_stream(h, &h->pipe_stream));
+            if (!h->ev_pscr[0]) {  // (the stream may exist already: a pipelined adaptive call shares it)
                 for (int i = 0; i < 2; ++i) {
                     HIP_TRY(hipEventCreateWithFlags(&h->ev_pscr[i], hipEventDisableTiming));
                     HIP_TRY(hipEventCreateWithFlags(&h->ev_px[i], hipEventDisableTiming));
@@ -758,9 +779,12 @@ int pscl_destroy(pscl_handle* h) {
         if (h->ev_px[i]) hipEventDestroy(h->ev_px[i]);
         if (h->ev_tscr[i]) hipEventDestroy(h->ev_tscr[i]);
         if (h->ev_tail[i]) hipEventDestroy(h->ev_tail[i]);
+        if (h->ev_adc[i]) hipEventDestroy(h->ev_adc[i]);
+        if (h->ev_ad[i]) hipEventDestroy(h->ev_ad[i]);
     }
     if (h->pipe_stream) hipStreamDestroy(h->pipe_stream);
     if (h->tail_stream) hipStreamDestroy(h->tail_stream);
+    if (h->ad_stream) hipStreamDestroy(h->ad_stream);
     if (h->stash_pipe) hipStreamDestroy(h->stash_pipe);
     for (int i = 0; i < kChainStreams; ++i) {
         if (h->stash_retry[i]) hipStreamDestroy(h->stash_retry[i]);
@@ -817,6 +841,7 @@ int pscl_decode_device(pscl_handle* h, const double* d_llr, int64_t B, const uin
     P.counters = d_counters;
     if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
     if (!h->pipelined && (rc = join_pipe(h))) return rc;
+    if (h->pipelined && (h->ad_pending[0] || h->ad_pending[1]) && (rc = join_pipe(h, 1))) return rc;  // (adaptive calls' stage 2)
     return launch_decode(h, P, hist, nullptr, 38, h->pipelined);
 }
 
@@ -1007,6 +1032,166 @@ int pscl_escalate_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
     return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, n);
 }
 
+namespace {
+
+// pscl_adaptive_async_device's scratch, by parity: + 0 the counts (deferred frames at int 0, escalated
+// frames at int 16), + 1 the escalated frames' row list, + 2 the deferred frames' row list, + 3 the
+// exact long-code kernel's workgroup scratch
+constexpr int kAdSlot[2] = {128, 132};
+
+// the start of an adaptive call without a host wait: its scratch parity (pipelined calls alternate),
+// and the handle's stream ordered behind the side-stream work that last used that parity -- and the
+// caller's buffers of the call two back -- before this call's SC stage writes anything
+int adaptive_begin(pscl_handle* h, bool pipe, int* par) {
+    const int q = pipe ? h->ad_par : 0;
+    if (pipe) {
+        if (!h->pipe_stream) HIP_TRY(create_priority_stream(h, &h->pipe_stream));
+        if (!h->ad_stream) HIP_TRY(create_priority_stream(h, &h->ad_stream));
+        for (int i = 0; i < 2; ++i) {
+            if (!h->ev_adc[i]) HIP_TRY(hipEventCreateWithFlags(&h->ev_adc[i], hipEventDisableTiming));
+            if (!h->ev_ad[i]) HIP_TRY(hipEventCreateWithFlags(&h->ev_ad[i], hipEventDisableTiming));
+        }
+        h->ad_par ^= 1;
+    }
+    if (h->ad_pending[q]) {
+        HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_ad[q], 0));
+        h->ad_pending[q] = false;
+    }
+    *par = q;
+    return PSCL_OK;
+}
+
+// Stage 2 without the host wait, after the SC stage on the handle's stream: the frames whose flags
+// lack PSCL_FLAG_CRC_PASS are compacted into a row list and a device count (dl_compact; no dense
+// buffers), and the list decoder runs on "the first count rows of the list, results at their rows":
+// the row-list screening launch (pscl_rowlist; its grid is sized for B, never by the count: the
+// workgroups past the count exit at once) and the exact re-decode of the frames it defers -- or, where the
+// handle's plain decode has no lane-per-path screening kernel, the exact kernel on the list itself.
+// Then (d_ref) the statistics of all B final outputs, and the escalated count from device memory.
+// pipe: everything after the compaction on parity q's side stream behind ev_adc[q]; ev_ad[q] marks its end.
+int adaptive_escalate_enqueue(pscl_handle* h, int q, bool pipe, const double* d_llr, int64_t B, uint64_t* d_best,
+                              uint8_t* d_flags, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                              int32_t* d_n_escalated) {
+    hipStream_t s = h->stream;
+    const int base = kAdSlot[q];
+    const int64_t regrown = h->n_regrow;
+    hipError_t e;
+    int rc;
+    void *d_cnt, *d_list, *d_amb;
+    if ((rc = ensure(h, base, 128, &d_cnt))) return rc;
+    if ((rc = ensure(h, base + 1, (size_t)B * 8, &d_list))) return rc;
+    if ((rc = ensure(h, base + 2, (size_t)B * 8, &d_amb))) return rc;
+    int32_t* const amb_cnt = (int32_t*)d_cnt;
+    int32_t* const esc_cnt = amb_cnt + 16;
+    pscl_decode_params P;
+    fill_decode_params(h, P, 0);
+    P.llr = d_llr;
+    P.B = B;
+    P.best = d_best;
+    P.flags = d_flags;
+    P.fidx = (const int64_t*)d_list;
+    P.d_count = esc_cnt;
+    P.out_by_row = 1;
+    if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
+    pscl_decode_params S = P;  // the row-list screening launch
+    S.apx = 1;
+    pscl_decode_layout(S, 0);
+    S.amb_list = (int64_t*)d_amb;
+    S.amb_count = amb_cnt;
+    S.grid_cap = h->tune[PSCL_TUNE_ADAPT_GRID];  // (0: sized for B -- measured faster than any resident cap)
+    const bool screen = h->screen && h->tune[PSCL_TUNE_LANE_EXACT] != 3 &&
+                        (S.long_mode ? pscl_lane_long_available(S) != 0
+                                     : (pscl_lane_available(S) != 0 || pscl_lane_long128_available(S) != 0));
+    pscl_decode_params X = P;  // the exact kernel: on the deferred frames, or on the row list itself
+    X.lane_exact = lane_exact_on(h) ? 1 : 0;
+    X.grid_cap = (int64_t)256 * 16 / (pscl_decode_wpg(X) > 0 ? pscl_decode_wpg(X) : 1);  // (one resident set, launch_decode)
+    if (screen) {
+        X.fidx = (const int64_t*)d_amb;
+        X.d_count = amb_cnt;
+    }
+    if (X.long_mode) {
+        void* d_scr;
+        if ((rc = ensure(h, base + 3, (size_t)pscl_decode_grid(X) * (size_t)X.long_block_bytes, &d_scr))) return rc;
+        X.long_scratch = (unsigned char*)d_scr;
+    }
+    h->n_ad_waits += h->n_regrow - regrown;  // (a regrown buffer drained the side streams on the host)
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 128, s));
+    if ((e = pscl_launch_dl_compact(d_flags, B, 0, (int64_t*)d_list, nullptr, esc_cnt, s)) != hipSuccess)
+        return fail(PSCL_EDEVICE, "dl_compact launch: %s", hipGetErrorString(e));
+    hipStream_t t = s;
+    if (pipe) {
+        t = q ? h->ad_stream : h->pipe_stream;
+        HIP_TRY(hipEventRecord(h->ev_adc[q], s));
+        HIP_TRY(hipStreamWaitEvent(t, h->ev_adc[q], 0));
+    }
+    if (screen) {
+        if ((e = pscl_launch_decode(S, 0, t)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "row-list decode launch: %s", hipGetErrorString(e));
+        h->screened = true;
+        h->screened_slot = base;
+        h->n_ad_screened++;
+    } else {
+        h->n_ad_exact++;
+    }
+    if (pscl_lane_exact_available(X)) h->n_lane_exact++;
+    if ((e = pscl_launch_decode(X, 0, t)) != hipSuccess)
+        return fail(PSCL_EDEVICE, "decode kernel launch: %s", hipGetErrorString(e));
+    if (d_ref && (e = pscl_launch_dl_count(d_best, d_flags, d_ref, B, h->W, k_payload, d_counters, t)) != hipSuccess)
+        return fail(PSCL_EDEVICE, "dl_count launch: %s", hipGetErrorString(e));
+    if ((d_ref || d_n_escalated) &&
+        (e = pscl_launch_publish_count(esc_cnt, d_ref ? d_counters : nullptr, PSCL_CNT_ESCALATED, d_n_escalated, t)) != hipSuccess)
+        return fail(PSCL_EDEVICE, "counter launch: %s", hipGetErrorString(e));
+    if (pipe) {
+        HIP_TRY(hipEventRecord(h->ev_ad[q], t));
+        h->ad_pending[q] = true;
+    }
+    return PSCL_OK;
+}
+
+// the argument checks the adaptive calls without a host wait share
+int adaptive_async_args(pscl_handle* h, int64_t B, int k_payload) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
+    if (!h->crc_poly) return fail(PSCL_EINVAL, "adaptive decoding needs a CRC (without one every SC result passes)");
+    if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
+    if (h->N < 32) return fail(PSCL_EUNSUP, "the SC stage is implemented for N = 32 .. %d (N = %d)", PSCL_MAX_N, h->N);
+    if (h->rm_E && h->N != PSCL_FAST_N)
+        return fail(PSCL_EUNSUP, "the SC stage takes rate-matched rows at N = %d only (N = %d)", PSCL_FAST_N, h->N);
+    if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
+    return PSCL_OK;
+}
+
+}  // namespace
+
+int pscl_adaptive_async_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                               uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                               int32_t* d_n_escalated) {
+    int rc = adaptive_async_args(h, B, k_payload);
+    if (rc) return rc;
+    if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
+    if (B > 0 && (!d_llr || !d_best || !d_flags)) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
+    const bool pipe = h->pipelined;
+    // (pending pipelined work first; a pipelined call orders the earlier adaptive calls by parity)
+    if ((rc = set_device(h)) || (rc = join_pipe(h, pipe ? 3 + 8 : 3))) return rc;
+    if (B == 0) {
+        if (d_n_escalated) HIP_TRY(hipMemsetAsync(d_n_escalated, 0, 4, h->stream));
+        return PSCL_OK;
+    }
+    int q = 0;
+    if ((rc = adaptive_begin(h, pipe, &q))) return rc;
+    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage))) return rc;
+    return adaptive_escalate_enqueue(h, q, pipe, d_llr, B, d_best, d_flags, d_ref, k_payload, d_counters, d_n_escalated);
+}
+
+int pscl_adaptive_stats(pscl_handle* h, int64_t* screened, int64_t* exact, int64_t* host_waits, int reset) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (screened) *screened = h->n_ad_screened;
+    if (exact) *exact = h->n_ad_exact;
+    if (host_waits) *host_waits = h->n_ad_waits;
+    if (reset) h->n_ad_screened = h->n_ad_exact = h->n_ad_waits = 0;
+    return PSCL_OK;
+}
+
 int pscl_join(pscl_handle* h) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     int rc = set_device(h);
@@ -1039,7 +1224,8 @@ int pscl_set_pipelined(pscl_handle* h, int enable) {
 int pscl_set_tuning(pscl_handle* h, int knob, int64_t value) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     static const int64_t lim[PSCL_TUNE_COUNT][2] = {{0, 0}, {0, 2}, {0, 64}, {0, 2}, {0, 1}, {0, 4096}, {0, PSCL_MAX_WAVES_PER_WG}, {0, 2},
-                                                    {0, (int64_t)1 << 30}, {0, 2}, {0, 32}, {0, 3}, {0, 2}, {0, 2}, {0, 4}, {0, 3}, {0, 2}, {0, 1}};
+                                                    {0, (int64_t)1 << 30}, {0, 2}, {0, 32}, {0, 3}, {0, 2}, {0, 2}, {0, 4}, {0, 3}, {0, 2}, {0, 1},
+                                                    {0, (int64_t)1 << 20}};
     if (knob < 1 || knob >= PSCL_TUNE_COUNT) return fail(PSCL_EINVAL, "unknown tuning knob %d", knob);
     if (value < lim[knob][0] || value > lim[knob][1] || (knob == PSCL_TUNE_POST_GRID && value && value < 16))
         return fail(PSCL_EINVAL, "tuning knob %d: value %lld out of range", knob, (long long)value);
@@ -2095,6 +2281,80 @@ int pscl_simulate(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno
     if ((rc = join_pipe(h))) return rc;  // (a pipelined handle: this call's chains, then the counters)
     HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(int64_t) * 3 * PSCL_NCOUNT, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return PSCL_OK;
+}
+
+namespace {
+// pscl_simulate_adaptive[_device]: chunks of at most 2^20 frames through handle scratch (slots
+// 136 .. 139: rows, messages, best words, flags), each = TX (+ the uncoded baseline), the SC stage,
+// its statistics (row 0), and the escalation without a host wait with the final statistics (row 1).
+// Stream-ordered on the handle's stream: consecutive chunks reuse the scratch in stream order.
+int simulate_adaptive_enqueue(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate, int k_payload,
+                              int64_t frame0, int64_t B, int include_uncoded, int64_t* cs) {
+    const int64_t chunk = B < (1 << 20) ? B : (1 << 20);
+    const int W = h->W;
+    const int64_t row = h->rm_E ? h->rm_E : h->N;
+    const int64_t regrown = h->n_regrow;
+    hipError_t e;
+    int rc;
+    void *d_llr, *d_msg, *d_best, *d_flags;
+    if ((rc = ensure(h, 136, (size_t)chunk * row * 8, &d_llr))) return rc;
+    if ((rc = ensure(h, 137, (size_t)chunk * W * 8, &d_msg))) return rc;
+    if ((rc = ensure(h, 138, (size_t)chunk * W * 8, &d_best))) return rc;
+    if ((rc = ensure(h, 139, (size_t)chunk, &d_flags))) return rc;
+    h->n_ad_waits += h->n_regrow - regrown;
+    for (int64_t f = 0; f < B; f += chunk) {
+        const int64_t n = B - f < chunk ? B - f : chunk;
+        // N <= 128: the uncoded baseline is counted by the TX launch itself (same payload draw)
+        const bool unc_fused = include_uncoded && h->N <= PSCL_FAST_N;
+        if ((rc = channel_launch(h, seed, stream_id, ebno_db, rate, k_payload, frame0 + f, n, (double*)d_llr,
+                                 (uint64_t*)d_msg, unc_fused ? cs + 2 * PSCL_NCOUNT : nullptr, true)))
+            return rc;
+        if (include_uncoded && !unc_fused &&
+            (rc = uncoded_launch(h, seed, stream_id, ebno_db, k_payload, frame0 + f, n, cs + 2 * PSCL_NCOUNT, true)))
+            return rc;
+        int q = 0;
+        if ((rc = adaptive_begin(h, false, &q))) return rc;
+        if ((rc = launch_sc_stage(h, (const double*)d_llr, n, (uint64_t*)d_best, (uint8_t*)d_flags, nullptr))) return rc;
+        if ((e = pscl_launch_dl_count((const uint64_t*)d_best, (const uint8_t*)d_flags, (const uint64_t*)d_msg, n, W,
+                                      k_payload, cs, h->stream)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "dl_count launch: %s", hipGetErrorString(e));
+        if ((rc = adaptive_escalate_enqueue(h, q, false, (const double*)d_llr, n, (uint64_t*)d_best, (uint8_t*)d_flags,
+                                            (const uint64_t*)d_msg, k_payload, cs + PSCL_NCOUNT, nullptr)))
+            return rc;
+    }
+    return PSCL_OK;
+}
+}  // namespace
+
+int pscl_simulate_adaptive_device(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate,
+                                  int k_payload, int64_t frame0, int64_t B, int include_uncoded, int64_t* d_counters) {
+    int rc = adaptive_async_args(h, B < 0 ? B : 0, k_payload);  // (any B: the chunks are at most 2^20 frames)
+    if (rc) return rc;
+    if (!d_counters) return fail(PSCL_EINVAL, "d_counters is NULL");
+    if (frame0 < 0) return fail(PSCL_EINVAL, "B and frame0 must be >= 0");
+    if (B == 0) return PSCL_OK;
+    if ((rc = enter(h))) return rc;
+    return simulate_adaptive_enqueue(h, seed, stream_id, ebno_db, rate, k_payload, frame0, B, include_uncoded, d_counters);
+}
+
+int pscl_simulate_adaptive(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate,
+                           int k_payload, int64_t frame0, int64_t B, int include_uncoded, int64_t* counters) {
+    int rc = adaptive_async_args(h, B < 0 ? B : 0, k_payload);
+    if (rc) return rc;
+    if (!counters) return fail(PSCL_EINVAL, "counters is NULL");
+    if (frame0 < 0) return fail(PSCL_EINVAL, "B and frame0 must be >= 0");
+    memset(counters, 0, sizeof(int64_t) * 3 * PSCL_NCOUNT);
+    if (B == 0) return PSCL_OK;
+    if ((rc = enter(h))) return rc;
+    void* d_cnt;
+    if ((rc = ensure(h, 140, sizeof(int64_t) * 3 * PSCL_NCOUNT, &d_cnt))) return rc;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * 3 * PSCL_NCOUNT, h->stream));
+    if ((rc = simulate_adaptive_enqueue(h, seed, stream_id, ebno_db, rate, k_payload, frame0, B, include_uncoded,
+                                        (int64_t*)d_cnt)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(int64_t) * 3 * PSCL_NCOUNT, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));  // the host form's one wait, at the end
     return PSCL_OK;
 }
 

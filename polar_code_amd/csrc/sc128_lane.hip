@@ -336,6 +336,16 @@ __global__ void sc_add_counter_kernel(int64_t* counters, int slot, int64_t v) {
         atomicAdd(reinterpret_cast<unsigned long long*>(counters) + slot, (unsigned long long)v);
 }
 
+// the escalated count of pscl_adaptive_async_device, read on the device: counters[slot] += *count
+// (counters may be null) and *out = *count (out may be null)
+__global__ void sc_publish_count_kernel(const int32_t* __restrict__ count, int64_t* counters, int slot, int32_t* out) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int32_t c = *count;
+        if (counters && c > 0) atomicAdd(reinterpret_cast<unsigned long long*>(counters) + slot, (unsigned long long)c);
+        if (out) *out = c;
+    }
+}
+
 }  // namespace
 
 int pscl_sc_lane_lds(const pscl_sc_params& P) {
@@ -383,5 +393,10 @@ hipError_t pscl_launch_scatter_results(const int64_t* act, int64_t n, int W, con
 
 hipError_t pscl_launch_add_counter(int64_t* counters, int slot, int64_t v, hipStream_t s) {
     hipLaunchKernelGGL(sc_add_counter_kernel, dim3(1), dim3(64), 0, s, counters, slot, v);
+    return hipGetLastError();
+}
+
+hipError_t pscl_launch_publish_count(const int32_t* count, int64_t* counters, int slot, int32_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(sc_publish_count_kernel, dim3(1), dim3(64), 0, s, count, counters, slot, out);
     return hipGetLastError();
 }

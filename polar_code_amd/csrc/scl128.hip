@@ -78,7 +78,8 @@ int pscl_screening_fs_available(const pscl_decode_params& P) {
 // the (128,64) code on plain channel rows or the NR (128,88) code on rate-matched rows
 // (PSCL_LANE_NR), L = 8 (and L = 4 unless PSCL_LANE4 = 0)
 int pscl_lane_available(const pscl_decode_params& P) {
-    if (!PSCL_LANE || !P.apx || P.no_lane || P.force || P.sc_hard || P.fidx || P.d_count || P.elist) return 0;
+    if (!PSCL_LANE || !P.apx || P.no_lane || P.force || P.sc_hard || P.elist) return 0;
+    if ((P.fidx || P.d_count) && !pscl_rowlist(P)) return 0;  // (a row list: the RL instances)
     if (P.L != 8 && (P.L != 4 || !PSCL_LANE4)) return 0;
     if (P.N != 128) return 0;
     const int code = spec_code(P);

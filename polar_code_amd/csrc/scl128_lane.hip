@@ -215,7 +215,13 @@ __device__ __forceinline__ void tx_frame_words(const pscl_decode_params& P, uint
 // tier), else by ranking the 2L children (each lane counts the keys below its two, DPP-free
 // shuffles over the frame's lanes) and routing the survivors through LDS slots; frozen phases
 // re-sort only when a metric fell below its predecessor's.  No certificates, no deferral.
-template <int LMAX, int CODE, bool FS = false, bool TXF = false, bool FP = false, bool EX = false>
+// RL: the ROW-LIST form of the plain screening decode (stage 2 of pscl_adaptive_async_device): frame i
+// of the launch, i < min(P.B, *P.d_count), reads LLR row P.fidx[i] and writes its outputs at that row;
+// a frame it defers is appended to P.amb_list by its ROW (the exact re-decode reads that list as its
+// own P.fidx).  It does not count (P.ref is ignored).  Instances of their own, in a code object of their
+// own (scl128_lane_rl.hip compiles this file with PSCL_LANE_RL_UNIT and launches only those): the other
+// instances' code does not change, and their code object holds no kernel it did not hold before.
+template <int LMAX, int CODE, bool FS = false, bool TXF = false, bool FP = false, bool EX = false, bool RL = false>
 __global__ void __launch_bounds__(64, TXF ? (LMAX == 8 ? PSCL_TX_WAVES : 2)
                                            : (FS && !FP && !EX && LMAX == 8) ? PSCL_FS_WAVES : PSCL_LANE_WAVES_PER_EU)
 scl_lane_kernel(const pscl_decode_params P) {
@@ -223,6 +229,7 @@ scl_lane_kernel(const pscl_decode_params P) {
     static_assert(!TXF || (!FS && CODE == 1), "fused TX: plain decodes of the (128,64) code");
     static_assert(!FP || (FS && CODE == 1), "fused post pass: the FS instance of the (128,64) code");
     static_assert(!EX || (!TXF && !FP), "the exact instance: plain re-decodes and forced-bit retry decodes");
+    static_assert(!RL || (!FS && !TXF && !FP && !EX), "the row-list form: plain screening decodes");
     using Ly = LaneLayout<LMAX>;
     constexpr int G = Ly::G, F = Ly::F, LOG_G = Ly::LOG_G;
     constexpr int EPL = 16 / G;                 // depth-3 elements per lane at a recompute
@@ -276,6 +283,8 @@ scl_lane_kernel(const pscl_decode_params P) {
         Bn = tot < P.B ? tot : P.B;
     } else if constexpr (EX) {  // (the re-decode: the first *d_count listed frames)
         if (P.d_count) Bn = *P.d_count < P.B ? (int64_t)*P.d_count : P.B;
+    } else if constexpr (RL) {  // (the first *d_count listed frames; a count of 0: nothing runs)
+        Bn = *P.d_count < P.B ? (int64_t)*P.d_count : P.B;
     }
     for (int64_t f0 = (int64_t)blockIdx.x * F; f0 < Bn; f0 += (int64_t)gridDim.x * F) {
         const int64_t fi = f0 + fl;
@@ -292,6 +301,8 @@ scl_lane_kernel(const pscl_decode_params P) {
             frow = P.fidx[f];
         } else if constexpr (EX) {
             if (P.fidx) frow = P.fidx[fsafe];
+        } else if constexpr (RL) {
+            frow = P.fidx[fsafe];
         }
         // CODE = 2 (the NR (128,88) code, config 5): the input rows are rate matched -- E received
         // LLRs, de-rate-matched and de-interleaved per position as the values are loaded
@@ -1240,7 +1251,7 @@ scl_lane_kernel(const pscl_decode_params P) {
                 P.amb_elist[(int64_t)fseg * P.bcap + slot] = (int32_t)f;
                 P.flags[f] = PSCL_DL_DEFERRED;
             } else {
-                P.amb_list[atomicAdd(P.amb_count, 1)] = fi;
+                P.amb_list[atomicAdd(P.amb_count, 1)] = RL ? frow : fi;  // (RL: the frame's row, not its list position)
             }
         }
         // best: the lowest list position whose candidate passes the CRC (position 0 if none)
@@ -1250,14 +1261,14 @@ scl_lane_kernel(const pscl_decode_params P) {
         if (fvalid && !famb && keyb == kbest) {
             const int best = (int)(kbest & (uint32_t)(LMAX - 1));
             const bool bpass = kbest < (uint32_t)LMAX;
-            const int64_t fo = (EX && !FS && P.out_by_row) ? frow : f;  // (the re-decode: at the frame's row)
+            const int64_t fo = (RL || (EX && !FS && P.out_by_row)) ? frow : f;  // (the re-decode, a row list: at the frame's row)
             if (P.best) {
                 P.best[fo * PW] = ib0;
                 if (PW > 1) P.best[fo * PW + 1] = ib1;
             }
             if (P.flags) P.flags[fo] = (uint8_t)((bpass ? PSCL_FLAG_CRC_PASS : 0u) | (uint32_t)best);
             if (P.n_paths) P.n_paths[fo] = FS ? (1 << lcnt) : LMAX;
-            if (!FS && P.ref) {
+            if (!FS && !RL && P.ref) {
                 const uint64_t ibw[2] = {ib0, ib1};
                 tally_errors(ibw, TXF ? tm : P.ref + fo * PW, PW, P.k_payload, bpass, cfe, cbe, cpe, cpb);
             }
@@ -1275,7 +1286,7 @@ scl_lane_kernel(const pscl_decode_params P) {
         }
         wave_lds_fence();
     }
-    if (!FS && P.ref) {
+    if (!FS && !RL && P.ref) {
         flush_counts_p(P, blockIdx.x, cfe, cbe, cpe, cpb);
         if (blockIdx.x == 0 && threadIdx.x == 0 && !(EX && P.out_by_row))  // (a re-decode's frames were counted)
             atomicAdd(reinterpret_cast<unsigned long long*>(P.counters) + PSCL_CNT_FRAMES, (unsigned long long)P.B);
@@ -1298,19 +1309,42 @@ scl_lane_kernel(const pscl_decode_params P) {
 
 }  // namespace
 
-// the lane-per-path screening launch of a plain (128,64) decode at L = 4 or 8: one wavefront of
-// 64 / L frames per workgroup, LDS = 30 L doubles per frame (15 KB per workgroup at both sizes)
-int pscl_lane_frames_per_wg(int L) { return 64 / L; }
-
 // timing-only: unused LDS bytes added to each plain launch (occupancy experiments; 0 in the product)
 #ifndef PSCL_LANE_LDS_PAD
 #define PSCL_LANE_LDS_PAD 0
 #endif
 
+#ifdef PSCL_LANE_RL_UNIT
+// the row-list instances of the plain screening decode (pscl_rowlist(P): stage 2 of
+// pscl_adaptive_async_device); the plain launch's LDS
+hipError_t pscl_launch_lane_rowlist(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
+    const int lds8 = LaneLayout<8>::F * LaneLayout<8>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD,
+              lds4 = LaneLayout<4>::F * LaneLayout<4>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD;
+    if (!pscl_rowlist(P)) return hipErrorInvalidValue;
+    const dim3 g((unsigned)grid), b(64);
+    if (P.L == 8 && !P.rm_E)
+        hipLaunchKernelGGL((scl_lane_kernel<8, 1, false, false, false, false, true>), g, b, lds8, s, P);
+    else if (P.L == 8)
+        hipLaunchKernelGGL((scl_lane_kernel<8, 2, false, false, false, false, true>), g, b, lds8, s, P);
+    else if (P.L == 4 && !P.rm_E)
+        hipLaunchKernelGGL((scl_lane_kernel<4, 1, false, false, false, false, true>), g, b, lds4, s, P);
+    else if (P.L == 4)
+        hipLaunchKernelGGL((scl_lane_kernel<4, 2, false, false, false, false, true>), g, b, lds4, s, P);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+#else
+
+// the lane-per-path screening launch of a plain (128,64) decode at L = 4 or 8: one wavefront of
+// 64 / L frames per workgroup, LDS = 30 L doubles per frame (15 KB per workgroup at both sizes)
+int pscl_lane_frames_per_wg(int L) { return 64 / L; }
+
 hipError_t pscl_launch_lane(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
     // (pscl_lane_available: the (128,64) code on plain rows, or the rate-matched NR (128,88) code)
     const int lds8 = LaneLayout<8>::F * LaneLayout<8>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD,
               lds4 = LaneLayout<4>::F * LaneLayout<4>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD;
+    if (pscl_rowlist(P)) return pscl_launch_lane_rowlist(P, grid, s);  // (scl128_lane_rl.hip)
     if (P.tx) {  // the fused TX instance (plain rows of the (128,64) code, pscl_simulate_device)
         if (P.rm_E) return hipErrorInvalidValue;
         if (P.L == 8)
@@ -1388,3 +1422,4 @@ hipError_t pscl_launch_lane_fs(const pscl_decode_params& P, int64_t grid, hipStr
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
+#endif  // PSCL_LANE_RL_UNIT

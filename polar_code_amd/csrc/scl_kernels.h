@@ -273,6 +273,9 @@ hipError_t pscl_launch_gather_rows(const double* llr, int64_t row, const int64_t
 hipError_t pscl_launch_scatter_results(const int64_t* act, int64_t n, int W, const uint64_t* best_in,
                                        const uint8_t* flags_in, uint64_t* best, uint8_t* flags, hipStream_t s);
 hipError_t pscl_launch_add_counter(int64_t* counters, int slot, int64_t v, hipStream_t s);
+// the same with the value in device memory (pscl_adaptive_async_device: no host read of the count):
+// counters[slot] += *count (counters may be null), *out = *count (out may be null)
+hipError_t pscl_launch_publish_count(const int32_t* count, int64_t* counters, int slot, int32_t* out, hipStream_t s);
 
 // Lane-parallel successive cancellation of the other code lengths (sc_lane.hip, N = 32, 64, 256,
 // 512, 1024; plain rows only): pscl_sc_device.  Outputs as pscl_sc_params'.
@@ -320,9 +323,20 @@ int pscl_screening_available(const pscl_decode_params& P);  // scl128.hip
 #ifndef PSCL_LANE4
 #define PSCL_LANE4 1
 #endif
+// a ROW-LIST screening launch (stage 2 of pscl_adaptive_async_device): frame i of the launch, for
+// i < min(B, *d_count), reads LLR row fidx[i] and writes best / flags at that row; the frames it
+// defers are appended to amb_list by their rows.  It counts nothing (dl_count_kernel counts
+// afterwards), and its grid never depends on the count: it is sized for B, the workgroups past the
+// count exit at once (grid_cap > 0, PSCL_TUNE_ADAPT_GRID: at most that many workgroups, striding over
+// the list).  Every other combination of fidx / d_count has no screening kernel.
+inline int pscl_rowlist(const pscl_decode_params& P) {
+    return P.apx && P.fidx && P.d_count && P.out_by_row && P.amb_list && P.amb_count && !P.force && !P.elist &&
+           !P.ref && !P.tx && !P.sc_hard;
+}
 int pscl_lane_available(const pscl_decode_params& P);
 int pscl_lane_frames_per_wg(int L);
 hipError_t pscl_launch_lane(const pscl_decode_params& P, int64_t grid, hipStream_t s);
+hipError_t pscl_launch_lane_rowlist(const pscl_decode_params& P, int64_t grid, hipStream_t s);  // scl128_lane_rl.hip
 // workgroups of a decode that adds its error counts with atomics (P.ref without P.cpart): each
 // wavefront strides over frames and adds its counts once at the end (lane-per-path kernels; the
 // two-lanes-per-path kernels' workgroups hold up to PSCL_MAX_WAVES_PER_WG wavefronts)

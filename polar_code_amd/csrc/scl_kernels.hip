@@ -613,7 +613,8 @@ hipError_t pscl_launch_decode(const pscl_decode_params& P, int hist, hipStream_t
         const int64_t g = (P.B + fw - 1) / fw;
         // (counting launches with atomics: at most PSCL_LANE_COUNT_GRID wavefronts, each adding its
         // frames' counts with one atomic per counter when it ends)
-        const int64_t cap = P.ref && !P.cpart ? PSCL_LANE_COUNT_GRID : (1 << 20);
+        int64_t cap = P.ref && !P.cpart ? PSCL_LANE_COUNT_GRID : (1 << 20);
+        if (P.grid_cap > 0 && P.grid_cap < cap) cap = P.grid_cap;  // (a row-list launch: resident workgroups)
         return pscl_launch_lane(P, g < 1 ? 1 : (g > cap ? cap : g), s);
     }
     if (!hist && pscl_lane_fs_available(P)) {  // (P.B: the round's entry capacity)

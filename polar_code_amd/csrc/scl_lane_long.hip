@@ -146,10 +146,16 @@ __global__ void __launch_bounds__(64, (NL == 10 || (NL == 9 && LMAX >= 16)) ? PS
     auto slot_rel = [](uint32_t tab, int dr) { return (int)((tab >> (SB * dr)) & ((1u << SB) - 1u)); };
 
     int cfe = 0, cbe = 0, cpe = 0, cpb = 0;  // this lane's error counts (flushed at the end)
-    for (int64_t f0 = (int64_t)blockIdx.x * F; f0 < P.B; f0 += (int64_t)gridDim.x * F) {
-        const int64_t fi = f0 + fl;
-        const bool fvalid = fi < P.B;
-        const int64_t frow = fvalid ? fi : f0;  // (a tail wave's empty slots decode a copy of frame f0)
+    // the row-list form (pscl_rowlist(P): stage 2 of pscl_adaptive_async_device) as a wave-uniform
+    // run-time branch of the same instances: frame i of the launch, i < min(P.B, *P.d_count), reads
+    // LLR row P.fidx[i], writes its outputs at that row and is deferred by its row
+    const int64_t Bn = P.d_count ? (*P.d_count < P.B ? (int64_t)*P.d_count : P.B) : P.B;
+    for (int64_t f0 = (int64_t)blockIdx.x * F; f0 < Bn; f0 += (int64_t)gridDim.x * F) {
+        const int64_t fpos = f0 + fl;
+        const bool fvalid = fpos < Bn;
+        const int64_t fsafe = fvalid ? fpos : f0;  // (a tail wave's empty slots decode a copy of frame f0)
+        const int64_t frow = P.fidx ? P.fidx[fsafe] : fsafe;
+        const int64_t fi = P.fidx ? frow : fpos;  // the frame's output row and its entry in the deferred list
         const double* chan = P.llr + frow * N;
         // the lane's depth-R elements e_h = p + G h (h < EPL) reduce ch[m] = chan[e_h + 16 m]
         double c[CREG ? EPL * CE : 1];
@@ -574,7 +580,8 @@ __global__ void __launch_bounds__(64, (NL == 10 || (NL == 9 && LMAX >= 16)) ? PS
 int64_t lane_long_grid(const pscl_decode_params& P) {
     const int F = 64 / P.L;
     const int64_t g0 = (P.B + F - 1) / F;
-    const int64_t cap = P.ref && !P.cpart ? PSCL_LANE_COUNT_GRID : (1 << 20);
+    int64_t cap = P.ref && !P.cpart ? PSCL_LANE_COUNT_GRID : (1 << 20);
+    if (P.grid_cap > 0 && P.grid_cap < cap) cap = P.grid_cap;  // (a row-list launch: resident workgroups)
     return g0 < 1 ? 1 : (g0 > cap ? cap : g0);
 }
 
@@ -597,8 +604,9 @@ hipError_t launch_lane_long(const pscl_decode_params& P, hipStream_t s) {
 // screening kernel: pscl_launch_decode takes the compiled-in ones first); L = 4 or 8, plain
 // channel rows, at least log2 L information bits (a full list)
 int pscl_lane_long_available(const pscl_decode_params& P) {
-    if (!PSCL_LANE_LONG || !P.apx || P.force || P.sc_hard || P.rm_E || P.fidx || P.d_count || P.elist) return 0;
-    if (!P.info_words || !P.epi_table || P.out_by_row) return 0;
+    if (!PSCL_LANE_LONG || !P.apx || P.force || P.sc_hard || P.rm_E || P.elist) return 0;
+    if ((P.fidx || P.d_count || P.out_by_row) && !pscl_rowlist(P)) return 0;  // (a row list: the run-time branch)
+    if (!P.info_words || !P.epi_table) return 0;
     if (P.L != 32 && P.L != 16 && P.L != 8 && P.L != 4) return 0;
     if (P.N != 128 && P.N != 256 && P.N != 512 && P.N != 1024) return 0;
     return P.K >= __builtin_ctz((unsigned)P.L);

@@ -144,6 +144,30 @@ class SCLDecoder:
             d_counters=counters.data_ptr() if counters is not None else 0)
         return best, flags, stage
 
+    def decode_tensor_adaptive_async(self, llr, ref_words=None, k_payload: int = 0, counters=None):
+        """decode_tensor_adaptive without the host wait (pscl_adaptive_async_device, N = 32 .. 1024):
+        everything is enqueued on the caller's current torch stream and the call returns.  Returns
+        (best_words [B, W] int64, flags [B] uint8, stage [B] uint8, n_escalated [1] int32) tensors;
+        with ref_words the final outputs' error statistics and the escalated count are added into
+        `counters` (int64[8] tensor)."""
+        import torch
+
+        row = self._dec.E or self.N
+        if llr.dtype != torch.float64 or not llr.is_contiguous() or llr.dim() != 2 or llr.shape[1] != row:
+            raise ValueError("llr must be a contiguous float64 [B, N] tensor")
+        B = llr.shape[0]
+        W = self._dec.W
+        best = torch.empty((B, W), dtype=torch.int64, device=llr.device)
+        flags = torch.empty((B,), dtype=torch.uint8, device=llr.device)
+        stage = torch.empty((B,), dtype=torch.uint8, device=llr.device)
+        n_esc = torch.empty((1,), dtype=torch.int32, device=llr.device)
+        self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
+        self._dec.adaptive_async_device(
+            llr.data_ptr(), B, d_best=best.data_ptr(), d_flags=flags.data_ptr(), d_stage=stage.data_ptr(),
+            d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
+            d_counters=counters.data_ptr() if counters is not None else 0, d_n_escalated=n_esc.data_ptr())
+        return best, flags, stage, n_esc
+
     def decode_sc(self, llr: np.ndarray):
         """sc_decode + check_crc on every frame (pscl_sc_device, N = 32 .. 1024): (bits [B, K] int8,
         crc_pass [B] bool)."""

@@ -17,6 +17,11 @@ synchronisation inside the timed region.  In one process, for the (128,64) code 
   t_stage2   the timed stage-2 decode launches per step (total timed launches minus t_sc)
   floor      the SC kernel's HBM floor: row bytes per frame at 6.29 TB/s
   model      t_sc + share * t_plain (the cost model of DESIGN.md section 5.9), beside the measured step
+  async      frames/s of Decoder.adaptive_async_device (no host wait, stage 2 a row-list launch) on the
+             same rows in the same run, on a plain handle and on a pipelined one (stage 2 on the side
+             stream); the synchronous call is the reference, timed --reps times, and its spread over
+             those repeats is the noise margin.  --grids: the async call again per workgroup cap of
+             the row-list launch (PSCL_TUNE_ADAPT_GRID; 1048576 = a grid sized for B)
 
 One JSON line per point, then a table.  python tools/bench_adaptive.py [--frames N] [--steps K]
 """
@@ -47,7 +52,7 @@ def timed(torch, dev, fn, steps, tail):
     return e0.elapsed_time(e1) / steps  # ms per step
 
 
-def run_point(torch, dev, N, K, L, E, ebno, B, steps, warmup, seed):
+def run_point(torch, dev, N, K, L, E, ebno, B, steps, warmup, seed, reps=3, grids=()):
     from polar_code_amd import _native
     from polar_code_amd.polar.polar import construct_info_set
 
@@ -95,6 +100,35 @@ def run_point(torch, dev, N, K, L, E, ebno, B, steps, warmup, seed):
     esc[0] = 0
     t_adaptive = timed(torch, dev, adaptive, steps, nothing)
     share = esc[0] / (steps * B)
+    # the call without the host wait, same rows, same run: reference and new call alternate
+    n_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def adaptive_async(i):
+        dec.adaptive_async_device(llr[i % nbuf].data_ptr(), B, d_best=best[i & 1].data_ptr(), d_flags=flags[i & 1].data_ptr(),
+                                  d_n_escalated=n_dev.data_ptr())
+
+    for i in range(warmup):
+        adaptive_async(i)
+    ref_ms, async_ms, async_pipe_ms = [t_adaptive], [], []
+    for r in range(reps):
+        if r:
+            ref_ms.append(timed(torch, dev, adaptive, steps, nothing))
+        async_ms.append(timed(torch, dev, adaptive_async, steps, nothing))
+    assert int(n_dev.cpu()[0]) > 0 or share == 0
+    dec.set_pipelined(True)
+    for i in range(warmup):
+        adaptive_async(i)
+    dec.join()
+    for r in range(reps):
+        async_pipe_ms.append(timed(torch, dev, adaptive_async, steps, dec.join))
+    dec.set_pipelined(False)
+    grid_ms = {}
+    for g in grids:
+        dec.set_tuning(adapt_grid=g)
+        adaptive_async(0)
+        grid_ms[str(g)] = min(timed(torch, dev, adaptive_async, steps, nothing) for _ in range(2))
+    dec.set_tuning(adapt_grid=0)
+    waits = dec.adaptive_stats()["host_waits"]
     # its timed launches: SC + the stage-2 decode
     dec.timing_enable(True)
     for i in range(steps):
@@ -123,6 +157,8 @@ def run_point(torch, dev, N, K, L, E, ebno, B, steps, warmup, seed):
         "escalated_share": share, "t_sc_ms": t_sc, "t_stage2_kernels_ms": t_stage2, "timed_launches_per_step": n_l / steps,
         "sc_hbm_floor_ms": floor_ms, "sc_over_floor": t_sc / floor_ms,
         "model_ms": t_sc + share * t_plain, "build_hash": _native.build_hash(),
+        "adaptive_ref_ms": ref_ms, "async_ms": async_ms, "async_pipelined_ms": async_pipe_ms, "async_grid_ms": grid_ms,
+        "async_fps": B / min(async_ms) * 1e3, "async_pipelined_fps": B / min(async_pipe_ms) * 1e3, "async_host_waits": waits,
     }
 
 
@@ -132,7 +168,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--reps", type=int, default=3, help="timed repeats of the synchronous reference and the async call")
+    ap.add_argument("--grids", type=str, default="", help="comma-separated workgroup caps of the row-list launch to time")
     args = ap.parse_args()
+    grids = [int(g) for g in args.grids.split(",") if g]
     import torch
 
     dev = torch.device("cuda", 0)
@@ -144,7 +183,8 @@ def main():
     stream = torch.cuda.Stream(dev)
     with torch.cuda.stream(stream):
         for N, K, L, E, ebno in points:
-            r = run_point(torch, dev, N, K, L, E, ebno, args.frames, max(args.steps, 1), args.warmup, args.seed)
+            r = run_point(torch, dev, N, K, L, E, ebno, args.frames, max(args.steps, 1), args.warmup, args.seed,
+                          max(args.reps, 1), grids)
             rows.append(r)
             print(json.dumps(r), flush=True)
     print()
@@ -156,6 +196,17 @@ def main():
               f"{r['adaptive_fps'] / 1e6:.0f} | {r['plain_fps'] / 1e6:.0f} | {r['plain_pipelined_fps'] / 1e6:.0f} | "
               f"{r['adaptive_ms']:.3f} | {r['t_sc_ms']:.3f} | {r['sc_hbm_floor_ms']:.3f} | {r['sc_over_floor']:.2f} | "
               f"{r['t_stage2_kernels_ms']:.3f} | {r['model_ms']:.3f} |")
+    print()
+    print("| code | dB | sync adaptive ms (min .. max of the repeats) | async ms | async pipelined ms | async Mf/s | "
+          "async pipelined Mf/s | host waits |")
+    print("|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['code']} L={r['L']} | {r['ebno_db']:.1f} | {min(r['adaptive_ref_ms']):.3f} .. {max(r['adaptive_ref_ms']):.3f} | "
+              f"{min(r['async_ms']):.3f} .. {max(r['async_ms']):.3f} | {min(r['async_pipelined_ms']):.3f} .. "
+              f"{max(r['async_pipelined_ms']):.3f} | {r['async_fps'] / 1e6:.0f} | {r['async_pipelined_fps'] / 1e6:.0f} | "
+              f"{r['async_host_waits']} |")
+        if r["async_grid_ms"]:
+            print("|  | row-list grid cap: " + ", ".join(f"{g}: {ms:.3f} ms" for g, ms in r["async_grid_ms"].items()) + " |")
 
 
 if __name__ == "__main__":

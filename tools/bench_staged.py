@@ -17,6 +17,9 @@ and (1024,512) at 6 dB:
   two handles  the same order with the batches alternating between two handles on two streams: the
                host wait of one batch's escalation then leaves the other batch's SC stage running
   plain        frames/s of the pipelined Decoder.decode_device (the unchanged baseline path)
+  async        frames/s of Decoder.adaptive_async_device (no host wait, stage 2 a row-list launch) on
+               the same rows in the same run, on a plain handle and on a pipelined one (stage 2 on the
+               side stream); `staged` is the reference, timed --reps times: its spread is the margin
 
 One JSON line per point, then a table.  python tools/bench_staged.py [--bytes N] [--steps K]
 """
@@ -54,7 +57,7 @@ def timed(torch, dev, fn, steps, tail):
     return e0.elapsed_time(e1) / steps  # ms per step
 
 
-def run_point(torch, dev, kind, N, K, L, ebno, B, steps, warmup, seed):
+def run_point(torch, dev, kind, N, K, L, ebno, B, steps, warmup, seed, reps=3):
     from polar_code_amd import _native
     from polar_code_amd.polar.polar import construct_info_set
 
@@ -114,6 +117,26 @@ def run_point(torch, dev, kind, N, K, L, ebno, B, steps, warmup, seed):
     esc[0] = 0
     t_staged = timed(torch, dev, staged, steps, nothing)
     share = esc[0] / (steps * B)
+    n_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def fused(i):
+        dec.adaptive_async_device(llr[i % nbuf].data_ptr(), B, **ptr[i & 1], d_n_escalated=n_dev.data_ptr())
+
+    for i in range(warmup):
+        fused(i)
+    ref_ms, async_ms, async_pipe_ms = [t_staged], [], []
+    for r in range(reps):
+        if r:
+            ref_ms.append(timed(torch, dev, staged, steps, nothing))
+        async_ms.append(timed(torch, dev, fused, steps, nothing))
+    dec.set_pipelined(True)
+    for i in range(warmup):
+        fused(i)
+    dec.join()
+    for r in range(reps):
+        async_pipe_ms.append(timed(torch, dev, fused, steps, dec.join))
+    dec.set_pipelined(False)
+    waits = dec.adaptive_stats()["host_waits"]
     sc(0)
     t_ahead = timed(torch, dev, staged_ahead, steps, nothing)
     for i in range(warmup):
@@ -141,6 +164,8 @@ def run_point(torch, dev, kind, N, K, L, ebno, B, steps, warmup, seed):
         "staged_ahead_fps": B / t_ahead * 1e3, "two_handles_ms": t_two, "two_handles_fps": B / t_two * 1e3,
         "plain_pipelined_ms": t_plain, "plain_pipelined_fps": B / t_plain * 1e3,
         "build_hash": _native.build_hash(),
+        "staged_ref_ms": ref_ms, "async_ms": async_ms, "async_pipelined_ms": async_pipe_ms,
+        "async_fps": B / min(async_ms) * 1e3, "async_pipelined_fps": B / min(async_pipe_ms) * 1e3, "async_host_waits": waits,
     }
 
 
@@ -151,6 +176,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--only", type=int, default=0, help="only the rows of this code length")
+    ap.add_argument("--reps", type=int, default=3, help="timed repeats of the staged reference and the async call")
     args = ap.parse_args()
     import torch
 
@@ -165,7 +191,7 @@ def main():
             if args.only and N != args.only:
                 continue
             B = max(1024, int(args.bytes // (N * 8)))
-            r = run_point(torch, dev, kind, N, K, 8, ebno, B, max(args.steps, 1), args.warmup, args.seed)
+            r = run_point(torch, dev, kind, N, K, 8, ebno, B, max(args.steps, 1), args.warmup, args.seed, max(args.reps, 1))
             rows.append(r)
             print(json.dumps(r), flush=True)
     print()
@@ -177,6 +203,15 @@ def main():
               f"{r['t_sc_ms']:.3f} | {r['sc_hbm_floor_ms']:.3f} | {r['sc_over_floor']:.1f} | {r['sc_fps'] / 1e6:.1f} | "
               f"{r['staged_fps'] / 1e6:.1f} | {r['staged_ahead_fps'] / 1e6:.1f} | {r['two_handles_fps'] / 1e6:.1f} | "
               f"{r['plain_pipelined_fps'] / 1e6:.1f} |")
+    print()
+    print("| code | set | dB | staged ms (min .. max of the repeats) | async ms | async pipelined ms | async Mf/s | "
+          "async pipelined Mf/s | two handles Mf/s | host waits |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['code']} L={r['L']} | {r['set']} | {r['ebno_db']:.1f} | {min(r['staged_ref_ms']):.3f} .. "
+              f"{max(r['staged_ref_ms']):.3f} | {min(r['async_ms']):.3f} .. {max(r['async_ms']):.3f} | "
+              f"{min(r['async_pipelined_ms']):.3f} .. {max(r['async_pipelined_ms']):.3f} | {r['async_fps'] / 1e6:.1f} | "
+              f"{r['async_pipelined_fps'] / 1e6:.1f} | {r['two_handles_fps'] / 1e6:.1f} | {r['async_host_waits']} |")
 
 
 if __name__ == "__main__":
