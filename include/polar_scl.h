@@ -340,6 +340,69 @@ int pscl_simulate_adaptive(pscl_handle* h, uint64_t seed, uint32_t stream_id, do
  */
 int pscl_adaptive_stats(pscl_handle* h, int64_t* screened, int64_t* exact, int64_t* host_waits, int reset);
 
+/*
+ * DL-SCL retry rounds on a baseline the caller already holds: flip.py:88-141 for every frame whose
+ * d_flags lacks PSCL_FLAG_CRC_PASS, the third building block next to pscl_sc_device and
+ * pscl_escalate_device.  Precondition: for every such frame d_best / d_flags hold what the handle's
+ * plain list decode returns for it -- pscl_decode_device, pscl_escalate_device and the adaptive
+ * calls leave exactly that.  The retry chains are pscl_dlscl_device's (same flip metric, tie rule
+ * and beta, pscl_set_beta; N > 128 decodes the listed frames again with decision-LLR history
+ * first); a frame with the pass flag never enters one and keeps its d_best / d_flags / d_stage.
+ *   d_attempts   NULL or [B] int32 out: 1 + flips tried (1 at the frames that do not enter)
+ *   d_tried      NULL or [B][tried_stride] int32 out: flip indices in order, -1 padded
+ *   d_stage      NULL or [B] uint8: 3 is written at every frame that enters a chain
+ *   d_ref        NULL or [B][W] transmitted words: the final outputs' statistics are added into
+ *                d_counters_dl (int64[PSCL_NCOUNT], required with d_ref) with PSCL_CNT_RETRIES
+ * Enqueued on the handle's stream; the call synchronizes once, for the failing count that sizes
+ * the chains.  On a pipelined handle pending work is ordered first and the call runs
+ * stream-ordered.  Any N <= 1024, L and rate matching that pscl_dlscl_device takes.
+ * PSCL_EINVAL without a CRC, for tried_stride < min(retries, K) and for d_ref without counters.
+ */
+int pscl_retry_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
+                      uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref,
+                      int k_payload, int64_t* d_counters_dl);
+
+/*
+ * Three-stage decode of a device batch: SC, the list decoder where SC fails the CRC, DL-SCL flips
+ * where the list decoder fails it too.  Per frame
+ *   u = sc_decode(llr); if check_crc(u): the result is u, stage 1, attempts 1;
+ *   otherwise the result is decode_with_retries(llr) (flip.py:65-141, baseline decode_scl): stage 2
+ *   and attempts 1 if that baseline passes the CRC, else stage 3 and attempts = 1 + flips tried.
+ * The composition of the two reference functions, bit for bit (best bits, CRC flag, best index of
+ * the final attempt, attempts, tried flips in order).  The baseline is pscl_adaptive_async_device's
+ * launches, stream-ordered on the handle's stream (no side stream), then pscl_dlscl_device's
+ * compaction, its one host wait for the failing count, and its retry chains; on a pipelined
+ * handle the chains are deferred and overlap the next call as pscl_dlscl_device's do (same buffer
+ * contract).  PSCL_TUNE_DL_CHUNKS does not apply (one chunk).
+ *   d_counters     with d_ref, int64 [3][PSCL_NCOUNT], ADDED: row 0 the SC results, row 1 the adaptive
+ *                  baseline with PSCL_CNT_ESCALATED, row 2 the final outputs with PSCL_CNT_RETRIES
+ *   d_n_escalated  NULL or a device int32: receives the escalated count
+ * retries <= 0 gives the adaptive result (stages 1 and 2, attempts 1).  Shapes and errors as
+ * pscl_adaptive_async_device's (N = 32 .. 1024, rate-matched rows at N = 128 only, a CRC required),
+ * and PSCL_EINVAL for tried_stride < min(retries, K).
+ */
+int pscl_adaptive_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best,
+                               uint8_t* d_flags, uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried,
+                               int tried_stride, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                               int32_t* d_n_escalated);
+
+/*
+ * One SNR point of a Monte-Carlo sweep with the three-stage decoder, for global frames
+ * [frame0, frame0 + B): the TX (and the optional uncoded baseline) with the Philox stream of
+ * pscl_simulate and pscl_simulate_adaptive -- shards add up exactly -- then
+ * pscl_adaptive_dlscl_device, over chunks of up to 2^20 frames in handle scratch (pscl_simulate's
+ * chunking; on a pipelined handle every chunk is one pipelined call).  Counters are ADDED into int64
+ * [4][PSCL_NCOUNT]: rows SC, adaptive (PSCL_CNT_ESCALATED), final (PSCL_CNT_RETRIES), uncoded.
+ * The device form's counters are zeroed by the caller and complete after pscl_join / pscl_sync; the
+ * host form zeroes, enqueues, waits and copies back.
+ */
+int pscl_simulate_adaptive_dl_device(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate,
+                                     int k_payload, int64_t frame0, int64_t B, int retries, int include_uncoded,
+                                     int64_t* d_counters);
+int pscl_simulate_adaptive_dl(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate,
+                              int k_payload, int64_t frame0, int64_t B, int retries, int include_uncoded,
+                              int64_t* counters);
+
 /* Device scratch helpers so that non-torch callers can drive the device path. */
 /*
  * One call per SNR point (the frame loop of run_fer_sweep.py:41-191 for global frames

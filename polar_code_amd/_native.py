@@ -46,6 +46,7 @@ EXPORTS = (
     "pscl_simulate_device", "pscl_adaptive_device", "pscl_decode_adaptive_cpu",
     "pscl_sc_device", "pscl_escalate_device",
     "pscl_adaptive_async_device", "pscl_simulate_adaptive", "pscl_simulate_adaptive_device", "pscl_adaptive_stats",
+    "pscl_retry_device", "pscl_adaptive_dlscl_device", "pscl_simulate_adaptive_dl", "pscl_simulate_adaptive_dl_device",
 )
 
 # pscl_set_tuning knobs (include/polar_scl.h)
@@ -123,6 +124,13 @@ def lib() -> C.CDLL:
         "pscl_simulate_adaptive_device": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, _vp]),
         "pscl_simulate_adaptive": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, _vp]),
         "pscl_adaptive_stats": (C.c_int, [_vp, P(_i64), P(_i64), P(_i64), C.c_int]),
+        "pscl_retry_device": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp]),
+        "pscl_adaptive_dlscl_device": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int,
+                                                 _vp, _vp]),
+        "pscl_simulate_adaptive_dl_device": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int,
+                                                       C.c_int, _vp]),
+        "pscl_simulate_adaptive_dl": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, C.c_int,
+                                                _vp]),
         "pscl_timing_read_split": (C.c_int, [_vp, P(_i64), P(_dbl), P(_i64), P(_dbl)]),
         "pscl_host_stats": (C.c_int, [_vp, P(_dbl), P(_dbl), P(_i64), C.c_int]),
         "pscl_path_stats": (C.c_int, [_vp, P(_i64), P(_i64), P(_i64), P(_i64), P(_i64)]),
@@ -315,9 +323,11 @@ class Decoder:
                                              int(k_payload), d_counters or None, C.byref(n)))
         return int(n.value)
 
-    def decode_adaptive(self, llr: np.ndarray) -> dict:
+    def decode_adaptive(self, llr: np.ndarray, retries: int = 0, beta=None) -> dict:
         """Host form of adaptive_device: llr [B, N] (or [B, E]) float64 -> dict(best_bits [B, K] int8,
-        crc_pass [B] bool, best_idx [B] int32, stage [B] uint8 (1 SC, 2 list), n_escalated)."""
+        crc_pass [B] bool, best_idx [B] int32, stage [B] uint8 (1 SC, 2 list), n_escalated).
+        retries > 0: the three-stage decode (adaptive_dlscl_device, flip metric beta) -- stage 3 where
+        flips were tried, and the keys attempts [B] int32 and tried [B, retries] int32 (-1 padded)."""
         llr = np.ascontiguousarray(llr, dtype=np.float64)
         if llr.ndim == 1:
             llr = llr[None, :]
@@ -325,6 +335,8 @@ class Decoder:
         if llr.shape[1] != (self.E or self.N):
             raise ValueError("Channel LLR length must be a power of two" if not self.E
                              else f"expected {self.E} rate-matched LLRs per frame")
+        if retries > 0:
+            return self._decode_three_stage(llr, B, int(retries), beta)
         with DeviceArena(self) as mem:
             d_llr = mem.alloc(max(llr.nbytes, 8))
             d_best = mem.alloc(max(B * self.W * 8, 8))
@@ -340,6 +352,33 @@ class Decoder:
         bits = ((words[:, j >> 6] >> (j & 63).astype(np.uint64)) & np.uint64(1)).astype(np.int8)
         return {"best_bits": bits, "crc_pass": (flags & PSCL_FLAG_CRC_PASS) != 0,
                 "best_idx": (flags & PSCL_FLAG_IDX_MASK).astype(np.int32), "stage": stage.copy(), "n_escalated": n}
+
+    def _decode_three_stage(self, llr: np.ndarray, B: int, R: int, beta) -> dict:
+        with DeviceArena(self) as mem:
+            d_llr = mem.alloc(max(llr.nbytes, 8))
+            d_best = mem.alloc(max(B * self.W * 8, 8))
+            d_flags = mem.alloc(max(B, 8))
+            d_stage = mem.alloc(max(B, 8))
+            d_att = mem.alloc(max(B * 4, 8))
+            d_tried = mem.alloc(max(B * R * 4, 8))
+            d_n = mem.alloc(8)
+            mem.memset(d_n, 0, 8)
+            if B:
+                mem.upload(d_llr, llr)
+            self.adaptive_dlscl_device(d_llr, B, R, beta=beta, d_best=d_best, d_flags=d_flags, d_stage=d_stage,
+                                       d_attempts=d_att, d_tried=d_tried, tried_stride=R, d_n_escalated=d_n)
+            self.sync()
+            words = mem.download(d_best, max(B * self.W * 8, 8), np.uint64)[:B * self.W].reshape(B, self.W)
+            flags = mem.download(d_flags, max(B, 8), np.uint8)[:B]
+            stage = mem.download(d_stage, max(B, 8), np.uint8)[:B]
+            att = mem.download(d_att, max(B * 4, 8), np.int32)[:B]
+            tried = mem.download(d_tried, max(B * R * 4, 8), np.int32)[:B * R].reshape(B, R)
+            n = int(mem.download(d_n, 8, np.int32)[0])
+        j = np.arange(self.K)
+        bits = ((words[:, j >> 6] >> (j & 63).astype(np.uint64)) & np.uint64(1)).astype(np.int8)
+        return {"best_bits": bits, "crc_pass": (flags & PSCL_FLAG_CRC_PASS) != 0,
+                "best_idx": (flags & PSCL_FLAG_IDX_MASK).astype(np.int32), "stage": stage.copy(), "n_escalated": n,
+                "attempts": att.copy(), "tried": tried.copy()}
 
     def sc_device(self, d_llr: int, B: int, *, d_best: int, d_flags: int, d_stage=0, d_ref=0, k_payload=0,
                   d_counters=0) -> None:
@@ -469,6 +508,30 @@ class Decoder:
                                           d_tried or None, int(tried_stride), d_ref or None, int(k_payload),
                                           d_counters_scl or None, d_counters_dl or None))
 
+    def retry_device(self, d_llr: int, B: int, retries: int, *, beta=None, d_best: int, d_flags: int, d_stage=0,
+                     d_attempts=0, d_tried=0, tried_stride=0, d_ref=0, k_payload=0, d_counters_dl=0) -> None:
+        """DL-SCL retry rounds on the baseline already in d_best / d_flags (pscl_retry_device): the
+        frames without the CRC-pass bit enter the chains, d_stage gets 3 there, the others are left alone."""
+        self.set_beta(beta)
+        with self._lock:
+            check(lib().pscl_retry_device(self._h, d_llr or None, int(B), int(retries), d_best or None, d_flags or None,
+                                          d_stage or None, d_attempts or None, d_tried or None, int(tried_stride),
+                                          d_ref or None, int(k_payload), d_counters_dl or None))
+
+    def adaptive_dlscl_device(self, d_llr: int, B: int, retries: int, *, beta=None, d_best: int, d_flags: int,
+                              d_stage=0, d_attempts=0, d_tried=0, tried_stride=0, d_ref=0, k_payload=0, d_counters=0,
+                              d_n_escalated=0) -> None:
+        """The three-stage decode (pscl_adaptive_dlscl_device): SC, the list decoder where SC fails the
+        CRC, DL-SCL flips where the list decoder fails it too.  d_counters: device int64
+        [3, PSCL_NCOUNT] (SC, adaptive, final), ADDED with d_ref.  On a pipelined handle the retry
+        chains are deferred (join() / sync() order them back), as dlscl_device's."""
+        self.set_beta(beta)
+        with self._lock:
+            check(lib().pscl_adaptive_dlscl_device(self._h, d_llr or None, int(B), int(retries), d_best or None,
+                                                   d_flags or None, d_stage or None, d_attempts or None, d_tried or None,
+                                                   int(tried_stride), d_ref or None, int(k_payload), d_counters or None,
+                                                   d_n_escalated or None))
+
     def uncoded_device(self, seed: int, stream_id: int, ebno_db: float, k_payload: int, frame0: int, B: int,
                        d_counters: int) -> None:
         check(lib().pscl_uncoded_device(self._h, int(seed) & (2**64 - 1), int(stream_id) & 0xFFFFFFFF,
@@ -516,6 +579,26 @@ class Decoder:
             check(lib().pscl_simulate_adaptive_device(self._h, int(seed) & (2**64 - 1), int(stream_id) & 0xFFFFFFFF,
                                                       float(ebno_db), float(rate), int(k_payload), int(frame0), int(B),
                                                       int(bool(include_uncoded)), d_counters or None))
+
+    def simulate_adaptive_dl(self, seed: int, stream_id: int, ebno_db: float, rate: float, k_payload: int, frame0: int,
+                             B: int, retries: int, include_uncoded: bool = False) -> np.ndarray:
+        """One SNR point with the three-stage decoder in one call (pscl_simulate_adaptive_dl): int64
+        counters [4, PSCL_NCOUNT], rows SC, adaptive (CNT_ESCALATED), final (CNT_RETRIES), uncoded."""
+        out = np.zeros((4, PSCL_NCOUNT), np.int64)
+        with self._lock:
+            check(lib().pscl_simulate_adaptive_dl(self._h, int(seed) & (2**64 - 1), int(stream_id) & 0xFFFFFFFF,
+                                                  float(ebno_db), float(rate), int(k_payload), int(frame0), int(B),
+                                                  int(retries), int(bool(include_uncoded)), out.ctypes.data))
+        return out
+
+    def simulate_adaptive_dl_device(self, seed: int, stream_id: int, ebno_db: float, rate: float, k_payload: int,
+                                    frame0: int, B: int, retries: int, include_uncoded: bool, d_counters: int) -> None:
+        """pscl_simulate_adaptive_dl enqueued, counters ADDED into device int64 [4, PSCL_NCOUNT] at
+        d_counters (complete after join() / sync())."""
+        with self._lock:
+            check(lib().pscl_simulate_adaptive_dl_device(self._h, int(seed) & (2**64 - 1), int(stream_id) & 0xFFFFFFFF,
+                                                         float(ebno_db), float(rate), int(k_payload), int(frame0), int(B),
+                                                         int(retries), int(bool(include_uncoded)), d_counters or None))
 
     def screening_count(self) -> int:
         """Frames the last screening decode handed to the exact re-decode (synchronizes)."""

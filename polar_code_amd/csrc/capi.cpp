@@ -101,6 +101,8 @@ struct pscl_dl_call {
     int64_t nch = 1, cap = 0;
     int nsplit = 2, pbase = 0;
     bool pipe = false;
+    int mode = 0;                 // the baseline (DlBase): 0 the list decode, 1 adaptive, 2 the caller's
+    uint8_t* d_stage = nullptr;   // (modes 1, 2) 3 at every frame that enters a chain
 };
 
 // depth of the DL-SCL pipeline (pscl_set_pipelined): a pipelined call's compaction output and, for
@@ -185,6 +187,7 @@ struct pscl_handle {
     // call), kDlPar for pscl_simulate_device's own scratch sets
     int dl_back = 2;
     pscl_dl_call dl_defer;            // the last pipelined call, its chains not yet enqueued
+    int dl_last_mode = 0;             // baseline mode of the last DL-SCL call (a change joins everything first)
     bool dl_defer_valid = false;
     std::vector<hipEvent_t> ev_pool;
     std::vector<uint8_t> ev_main;     // per timed launch: 1 if it ran on the handle's stream
@@ -1748,6 +1751,9 @@ int dl_chain(pscl_handle* h, const pscl_dl_call& a, const DlBufs& b, int64_t c, 
     if (h->N > PSCL_FAST_N) {
         if (A > 0) {
             HIP_TRY(hipStreamWaitEvent(h->retry_stream[0], h->ev_base[p], 0));
+            hipError_t e;
+            if (a.d_stage && (e = pscl_launch_dl_mark_stage(b.act[p], A, a.d_stage, 3, h->retry_stream[0])) != hipSuccess)
+                return fail(PSCL_EDEVICE, "stage launch: %s", hipGetErrorString(e));
             int r2 = dl_retry_long(h, b.LS, b.act[p], b.cnt[p], A, a.rounds, a.d_llr, a.d_best, a.d_flags, a.d_attempts,
                                    a.d_tried, a.tried_stride, d_cdl, h->retry_stream[0]);
             if (r2) return r2;
@@ -1765,6 +1771,9 @@ int dl_chain(pscl_handle* h, const pscl_dl_call& a, const DlBufs& b, int64_t c, 
         HIP_TRY(hipStreamWaitEvent(h->retry_stream[cs + k], h->ev_base[p], 0));
         DlState T = b.S[cs + k];
         T.act = b.act[p] + (k ? A0 : 0);
+        hipError_t e;
+        if (a.d_stage && (e = pscl_launch_dl_mark_stage(T.act, nk, a.d_stage, 3, h->retry_stream[cs + k])) != hipSuccess)
+            return fail(PSCL_EDEVICE, "stage launch: %s", hipGetErrorString(e));
         int r2 = dl_retry_chunk(h, T, k ? A - A0 : A0, a.rounds, a.d_llr, a.d_best, a.d_flags, a.d_attempts,
                                 a.d_tried, a.tried_stride, d_cdl, h->retry_stream[cs + k],
                                 (h->tune[PSCL_TUNE_DL_STREAMS] & 1) ? h->retry_stream[cs + k] : h->side_stream[cs + k],
@@ -1814,9 +1823,21 @@ struct TxSpec {
     uint64_t* msg = nullptr;
     int64_t* unc = nullptr;  // [PSCL_NCOUNT] or null
 };
+// the baseline the retry chains start from.  mode 0: the plain list decode of all B frames
+// (pscl_dlscl_device).  mode 1: the adaptive baseline without a host wait, stream-ordered on the
+// handle's stream -- the SC stage, its statistics (d_counters_sc), the escalation
+// (adaptive_escalate_enqueue; its statistics go where mode 0 counts the baseline, d_counters_scl).
+// mode 2: none, the caller's d_best / d_flags are the baseline (pscl_retry_device).  Modes 1 and 2
+// run one chunk without the fused TX and mark d_stage 3 over each chain's entry list.
+struct DlBase {
+    int mode = 0;
+    uint8_t* d_stage = nullptr;
+    int64_t* d_counters_sc = nullptr;
+    int32_t* d_n_escalated = nullptr;
+};
 int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
                int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref, int k_payload,
-               int64_t* d_counters_scl, int64_t* d_counters_dl, const TxSpec* tx);
+               int64_t* d_counters_scl, int64_t* d_counters_dl, const TxSpec* tx, const DlBase& base = DlBase());
 }  // namespace
 
 #ifndef PSCL_DL_TAIL_STREAM
@@ -1830,15 +1851,53 @@ int pscl_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, int retrie
                       d_counters_scl, d_counters_dl, nullptr);
 }
 
+// Retry rounds on the caller's baseline (include/polar_scl.h): dlscl_impl with the baseline skipped.
+int pscl_retry_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
+                      uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref,
+                      int k_payload, int64_t* d_counters_dl) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (!h->crc_poly) return fail(PSCL_EINVAL, "retry rounds need a CRC (without one every baseline passes)");
+    if (d_ref && !d_counters_dl) return fail(PSCL_EINVAL, "d_ref given without d_counters_dl");
+    DlBase base;
+    base.mode = 2;
+    base.d_stage = d_stage;
+    return dlscl_impl(h, d_llr, B, retries, d_best, d_flags, d_attempts, d_tried, tried_stride, d_ref, k_payload, nullptr,
+                      d_counters_dl, nullptr, base);
+}
+
+// The three-stage decode (include/polar_scl.h): dlscl_impl on the adaptive baseline.
+int pscl_adaptive_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best,
+                               uint8_t* d_flags, uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried,
+                               int tried_stride, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                               int32_t* d_n_escalated) {
+    int rc = adaptive_async_args(h, B, k_payload);
+    if (rc) return rc;
+    if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
+    if (B == 0) {
+        if ((rc = enter(h))) return rc;
+        if (d_n_escalated) HIP_TRY(hipMemsetAsync(d_n_escalated, 0, 4, h->stream));
+        return PSCL_OK;
+    }
+    DlBase base;
+    base.mode = 1;
+    base.d_stage = d_stage;
+    base.d_counters_sc = d_counters;
+    base.d_n_escalated = d_n_escalated;
+    return dlscl_impl(h, d_llr, B, retries, d_best, d_flags, d_attempts, d_tried, tried_stride, d_ref, k_payload,
+                      d_counters ? d_counters + PSCL_NCOUNT : nullptr, d_counters ? d_counters + 2 * PSCL_NCOUNT : nullptr,
+                      nullptr, base);
+}
+
 namespace {
 int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
                int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref, int k_payload,
-               int64_t* d_counters_scl, int64_t* d_counters_dl, const TxSpec* tx) {
+               int64_t* d_counters_scl, int64_t* d_counters_dl, const TxSpec* tx, const DlBase& base) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
     if (B == 0) return PSCL_OK;
     if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
-    if (d_ref && (!d_counters_scl || !d_counters_dl)) return fail(PSCL_EINVAL, "d_ref given without both counters");
+    const int mode = base.mode;
+    if (d_ref && ((!d_counters_scl && mode != 2) || !d_counters_dl)) return fail(PSCL_EINVAL, "d_ref given without both counters");
     if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
     const int rounds = h->crc_poly && retries > 0 ? (retries < h->K ? retries : h->K) : 0;
     if (d_tried && tried_stride < rounds) return fail(PSCL_EINVAL, "tried_stride < min(retries, K)");
@@ -1865,6 +1924,8 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
     a.d_ref = d_ref;
     a.k_payload = k_payload;
     a.d_counters_dl = d_counters_dl;
+    a.mode = mode;
+    a.d_stage = mode ? base.d_stage : nullptr;
     // Chunks (tuning knob PSCL_TUNE_DL_CHUNKS, default 1): the baseline decodes run in order on the handle's
     // stream; the retry entries of chunk c are split over two chains, each on its own retry
     // stream with its own state, so the two chains' rounds overlap each other (and chunk c + 1's
@@ -1876,7 +1937,7 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
     // 2.65 -> 2.38 ms/step with one).
     a.nch = 1;
     a.nsplit = h->N > PSCL_FAST_N ? 0 : (h->pipelined ? 1 : 2);
-    if (rounds > 0 && h->tune[PSCL_TUNE_DL_CHUNKS]) a.nch = h->tune[PSCL_TUNE_DL_CHUNKS];
+    if (rounds > 0 && h->tune[PSCL_TUNE_DL_CHUNKS] && !mode) a.nch = h->tune[PSCL_TUNE_DL_CHUNKS];
     if (rounds > 0 && h->N <= PSCL_FAST_N && h->tune[PSCL_TUNE_DL_SPLIT]) a.nsplit = (int)h->tune[PSCL_TUNE_DL_SPLIT];
     a.cap = (B + a.nch - 1) / a.nch;
     // Pipelined (pscl_set_pipelined, one chunk): the call enqueues its baseline, then the retry
@@ -1884,13 +1945,15 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
     // waits only for that one), and leaves its own chains to the next call or join -- so the
     // handle's stream holds back-to-back baselines and the chains (high-priority streams) run
     // beside them, the host never waiting for the baseline it has just enqueued.
-    a.pipe = h->pipelined && rounds > 0 && a.nch == 1;
+    a.pipe = h->pipelined && rounds > 0 && a.nch == 1 && mode != 2;  // (pscl_retry_device runs stream-ordered)
     if (h->dl_defer_valid &&
         (!a.pipe || h->dl_defer.B != B || h->dl_defer.rounds != rounds || h->dl_defer.nsplit != a.nsplit)) {
         // (a different shape: the pending chains first, their state sized as they were)
         if ((rc = dl_enqueue_deferred(h))) return rc;
     }
-    if ((rc = join_pipe(h, a.pipe ? 1 : 3))) return rc;
+    // (another baseline than the last call's: every pending tail and chain first)
+    if ((rc = join_pipe(h, a.pipe && mode == h->dl_last_mode ? 1 : 3))) return rc;
+    h->dl_last_mode = mode;
     a.pbase = a.pipe ? h->dl_par : 0;  // compaction parity of chunk 0
     if (a.pipe) {
         // the chains of the call dl_back calls back may still write their call's outputs (and, kDlPar
@@ -1963,7 +2026,7 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
         // call's baseline follows this one's screening pass directly
         hipStream_t ts = s;
         const int tpar = a.pbase & 1;
-        if (a.pipe && PSCL_DL_TAIL_STREAM && !h->tune[PSCL_TUNE_DL_TAIL]) {
+        if (a.pipe && !mode && PSCL_DL_TAIL_STREAM && !h->tune[PSCL_TUNE_DL_TAIL]) {
             if (!h->tail_stream) {
                 HIP_TRY(create_priority_stream(h, &h->tail_stream));
                 for (int i = 0; i < 2; ++i) {
@@ -1973,7 +2036,33 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
             }
             ts = h->tail_stream;
         }
-        if ((rc = launch_decode(h, P, 0, s, 38, false, ts != s ? ts : nullptr, tpar))) return rc;
+        if (mode == 1) {
+            int q = 0;
+            if ((rc = adaptive_begin(h, false, &q))) return rc;
+            if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, base.d_stage))) return rc;
+            if (d_ref && (e = pscl_launch_dl_count(d_best, d_flags, d_ref, B, W, k_payload, base.d_counters_sc, s)) != hipSuccess)
+                return fail(PSCL_EDEVICE, "dl_count launch: %s", hipGetErrorString(e));
+            hipEvent_t t0 = nullptr, t1 = nullptr;
+            if (h->timing) {  // (stage 2 -- compaction, row-list decode, re-decode, statistics -- as one timed launch)
+                while (h->ev_pool.size() < h->ev_used + 2) {
+                    hipEvent_t ev;
+                    HIP_TRY(hipEventCreate(&ev));
+                    h->ev_pool.push_back(ev);
+                }
+                t0 = h->ev_pool[h->ev_used];
+                t1 = h->ev_pool[h->ev_used + 1];
+                if (h->ev_main.size() < h->ev_pool.size() / 2) h->ev_main.resize(h->ev_pool.size() / 2);
+                h->ev_main[h->ev_used / 2] = 1;
+                h->ev_used += 2;
+                HIP_TRY(hipEventRecord(t0, s));
+            }
+            if ((rc = adaptive_escalate_enqueue(h, q, false, d_llr, B, d_best, d_flags, d_ref, k_payload, d_counters_scl,
+                                                base.d_n_escalated)))
+                return rc;
+            if (t1) HIP_TRY(hipEventRecord(t1, s));
+        } else if (mode == 0) {
+            if ((rc = launch_decode(h, P, 0, s, 38, false, ts != s ? ts : nullptr, tpar))) return rc;
+        }
         if (ts != s && rounds <= 0) {  // (no compaction: the tail ends with the re-decode)
             HIP_TRY(hipEventRecord(h->ev_tail[tpar], ts));
             h->tail_pending[tpar] = true;
@@ -2181,8 +2270,11 @@ bool tx_fused_applies(const pscl_handle* h, int k_payload) {
 // chains overlap the next chunk's (or the next point's) TX and baseline, so kDlPar scratch sets
 // rotate with the DL-SCL call parity, and a set is rewritten only after the chains of the call
 // kDlPar back that used it have ended.
+// adaptive (pscl_simulate_adaptive_dl[_device]): every chunk is a three-stage call instead -- no fused
+// TX, and cs has four rows: SC, adaptive baseline, final, uncoded.
 int simulate_enqueue(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate, int k_payload,
-                     int64_t frame0, int64_t B, int retries, int include_uncoded, int64_t* cs) {
+                     int64_t frame0, int64_t B, int retries, int include_uncoded, int64_t* cs, bool adaptive = false) {
+    int64_t* const cs_unc = cs + (adaptive ? 3 : 2) * PSCL_NCOUNT;
     const int64_t chunk = B < (1 << 20) ? B : (1 << 20);
     const int W = h->W, N = h->N;
     // (a rate-matched handle: the TX launch writes, and dlscl_impl reads, rows of rm_E doubles; the
@@ -2215,7 +2307,7 @@ int simulate_enqueue(pscl_handle* h, uint64_t seed, uint32_t stream_id, double e
         // the fused TX (PSCL_TUNE_TX_FUSED): the baseline decode draws the rows itself -- where its
         // screening launch is the lane kernel of the (128,64) code on plain rows
         TxSpec tx;
-        const bool fused = tx_fused_applies(h, k_payload);
+        const bool fused = !adaptive && tx_fused_applies(h, k_payload);
         if (fused) {
             h->n_fused_tx++;
             tx.k0 = (uint32_t)seed;
@@ -2229,21 +2321,29 @@ int simulate_enqueue(pscl_handle* h, uint64_t seed, uint32_t stream_id, double e
             tx.kp = k_payload;
             tx.rows = (double*)d_llr;
             tx.msg = (uint64_t*)d_msg;
-            tx.unc = include_uncoded ? cs + 2 * PSCL_NCOUNT : nullptr;
+            tx.unc = include_uncoded ? cs_unc : nullptr;
         } else {
             // N <= 128: the uncoded baseline is counted by the TX launch itself (same payload draw)
             const bool unc_fused = include_uncoded && N <= PSCL_FAST_N;
             if ((rc = channel_launch(h, seed, stream_id, ebno_db, rate, k_payload, frame0 + f, n, (double*)d_llr,
-                                     (uint64_t*)d_msg, unc_fused ? cs + 2 * PSCL_NCOUNT : nullptr, true)))
+                                     (uint64_t*)d_msg, unc_fused ? cs_unc : nullptr, true)))
                 return rc;
             if (include_uncoded && !unc_fused &&
-                (rc = uncoded_launch(h, seed, stream_id, ebno_db, k_payload, frame0 + f, n, cs + 2 * PSCL_NCOUNT, true)))
+                (rc = uncoded_launch(h, seed, stream_id, ebno_db, k_payload, frame0 + f, n, cs_unc, true)))
                 return rc;
         }
         const int back = h->dl_back;
         h->dl_back = kDlPar;  // (its own scratch set: kDlPar sets rotate with the call parity)
-        rc = dlscl_impl(h, (const double*)d_llr, n, retries, (uint64_t*)d_best, (uint8_t*)d_flags, nullptr, nullptr, 0,
-                        (const uint64_t*)d_msg, k_payload, cs, cs + PSCL_NCOUNT, fused ? &tx : nullptr);
+        if (adaptive) {
+            DlBase base;
+            base.mode = 1;
+            base.d_counters_sc = cs;
+            rc = dlscl_impl(h, (const double*)d_llr, n, retries, (uint64_t*)d_best, (uint8_t*)d_flags, nullptr, nullptr, 0,
+                            (const uint64_t*)d_msg, k_payload, cs + PSCL_NCOUNT, cs + 2 * PSCL_NCOUNT, nullptr, base);
+        } else {
+            rc = dlscl_impl(h, (const double*)d_llr, n, retries, (uint64_t*)d_best, (uint8_t*)d_flags, nullptr, nullptr, 0,
+                            (const uint64_t*)d_msg, k_payload, cs, cs + PSCL_NCOUNT, fused ? &tx : nullptr);
+        }
         h->dl_back = back;
         if (rc) return rc;
     }
@@ -2280,6 +2380,41 @@ int pscl_simulate(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno
         return rc;
     if ((rc = join_pipe(h))) return rc;  // (a pipelined handle: this call's chains, then the counters)
     HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(int64_t) * 3 * PSCL_NCOUNT, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return PSCL_OK;
+}
+
+int pscl_simulate_adaptive_dl_device(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate,
+                                     int k_payload, int64_t frame0, int64_t B, int retries, int include_uncoded,
+                                     int64_t* d_counters) {
+    int rc = adaptive_async_args(h, B < 0 ? B : 0, k_payload);  // (any B: the chunks are at most 2^20 frames)
+    if (rc) return rc;
+    if (!d_counters) return fail(PSCL_EINVAL, "d_counters is NULL");
+    if (frame0 < 0) return fail(PSCL_EINVAL, "B and frame0 must be >= 0");
+    if (B == 0) return PSCL_OK;
+    if ((rc = set_device(h)) || (rc = join_pipe(h, 1))) return rc;  // (DL chains keep overlapping, pscl_simulate_device)
+    return simulate_enqueue(h, seed, stream_id, ebno_db, rate, k_payload, frame0, B, retries, include_uncoded, d_counters,
+                            true);
+}
+
+int pscl_simulate_adaptive_dl(pscl_handle* h, uint64_t seed, uint32_t stream_id, double ebno_db, double rate,
+                              int k_payload, int64_t frame0, int64_t B, int retries, int include_uncoded,
+                              int64_t* counters) {
+    int rc = adaptive_async_args(h, B < 0 ? B : 0, k_payload);
+    if (rc) return rc;
+    if (!counters) return fail(PSCL_EINVAL, "counters is NULL");
+    if (frame0 < 0) return fail(PSCL_EINVAL, "B and frame0 must be >= 0");
+    memset(counters, 0, sizeof(int64_t) * 4 * PSCL_NCOUNT);
+    if (B == 0) return PSCL_OK;
+    if ((rc = enter(h))) return rc;
+    void* d_cnt;
+    if ((rc = ensure(h, 141, sizeof(int64_t) * 4 * PSCL_NCOUNT, &d_cnt))) return rc;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * 4 * PSCL_NCOUNT, h->stream));
+    if ((rc = simulate_enqueue(h, seed, stream_id, ebno_db, rate, k_payload, frame0, B, retries, include_uncoded,
+                               (int64_t*)d_cnt, true)))
+        return rc;
+    if ((rc = join_pipe(h))) return rc;  // (a pipelined handle: this call's chains, then the counters)
+    HIP_TRY(hipMemcpyAsync(counters, d_cnt, sizeof(int64_t) * 4 * PSCL_NCOUNT, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return PSCL_OK;
 }

@@ -1035,7 +1035,23 @@ __global__ void __launch_bounds__(256) dl_count_kernel(const uint64_t* __restric
     }
 }
 
+// stage[act[i]] = value over a chain's entry list (the three-stage decode marks stage 3; act holds
+// frame indices below the call's B, written by dl_compact_kernel)
+__global__ void __launch_bounds__(256) dl_mark_stage_kernel(const int64_t* __restrict__ act, int64_t n,
+                                                            uint8_t* __restrict__ stage, int value) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        stage[act[i]] = (uint8_t)value;
+}
+
 }  // namespace
+
+hipError_t pscl_launch_dl_mark_stage(const int64_t* act, int64_t n, uint8_t* stage, int value, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    int64_t grid = (n + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(dl_mark_stage_kernel, dim3((unsigned)grid), dim3(256), 0, s, act, n, stage, value);
+    return hipGetLastError();
+}
 
 hipError_t pscl_launch_dl_post_long(const pscl_post_long_params& Q, hipStream_t s) {
     if (Q.cap <= 0) return hipSuccess;

@@ -387,6 +387,8 @@ hipError_t pscl_launch_uncoded(const pscl_channel_params& P, int64_t* counters, 
 hipError_t pscl_launch_dl_compact(const uint8_t* flags, int64_t B, int64_t base, int64_t* act, int32_t* list,
                                   int32_t* count, hipStream_t s);
 hipError_t pscl_launch_iota64(int64_t* out, int64_t n, hipStream_t s);
+// stage[act[i]] = value, i < n (the three-stage decode: 3 over a retry chain's entry list)
+hipError_t pscl_launch_dl_mark_stage(const int64_t* act, int64_t n, uint8_t* stage, int value, hipStream_t s);
 hipError_t pscl_launch_replay(const pscl_replay_params& R, int64_t cap, hipStream_t s);
 hipError_t pscl_launch_tail_abs_scan(uint32_t lo, uint32_t hi, const uint64_t* exp_table, unsigned long long* out,
                                      hipStream_t s, int bits);

@@ -173,7 +173,7 @@ def words_to_bits(words: np.ndarray, K: int) -> np.ndarray:
 
 def decode_with_retries_device(llr: np.ndarray, info_set, M: int, retries: int, *, crc=None, beta=None,
                                device: int = 0, msg: Optional[np.ndarray] = None,
-                               tuning: Optional[dict] = None) -> dict:
+                               tuning: Optional[dict] = None, baseline: str = "scl") -> dict:
     """decode_with_retries for a batch [B, N] with the retry loop on the GPU.
 
     Returns best_bits [B, K] (final attempt), success [B], attempts [B], tried [B, R]
@@ -181,7 +181,14 @@ def decode_with_retries_device(llr: np.ndarray, info_set, M: int, retries: int, 
     `msg` [B, K] the in-kernel counters {"scl": [...], "dl": [...]} (PSCL_CNT_* order).
     `tuning`: schedule knobs for this call (Decoder.set_tuning; the handle's previous values,
     e.g. knobs a caller set on the shared decoder, are restored after).
+    `baseline`: "scl" (plain list decode of every frame) or "adaptive" -- SC first, the list decoder
+    where SC fails the CRC, flips where the list decoder fails it too (pscl_adaptive_dlscl_device;
+    needs a CRC).  Then base_bits / base_pass are the adaptive baseline's, the dict gains stage [B]
+    (1 SC, 2 list, 3 flips) and n_escalated, and the counters the key "sc" beside "scl" (the
+    adaptive baseline, with PSCL_CNT_ESCALATED) and "dl".
     """
+    if baseline not in ("scl", "adaptive"):
+        raise ValueError("baseline must be 'scl' or 'adaptive'")
     llr = np.ascontiguousarray(llr, dtype=np.float64)
     B, N = llr.shape
     info_set = np.asarray(info_set)
@@ -194,7 +201,10 @@ def decode_with_retries_device(llr: np.ndarray, info_set, M: int, retries: int, 
     if tuning:
         dec.set_tuning(**tuning)
     try:
-        _retries_device(dec, llr, B, W, R, K, retries, crc, beta, msg, out)
+        if baseline == "adaptive":
+            _retries_adaptive_device(dec, llr, B, W, R, K, retries, beta, msg, out)
+        else:
+            _retries_device(dec, llr, B, W, R, K, retries, crc, beta, msg, out)
     finally:
         if tuning:
             dec.set_tuning(**{k: prev.get(k, 0) for k in tuning})
@@ -236,6 +246,46 @@ def _retries_device(dec, llr, B, W, R, K, retries, crc, beta, msg, out) -> None:
         if msg is not None:
             out["counters"] = {"scl": mem.download(d_cs, _native.PSCL_NCOUNT * 8, np.int64),
                                "dl": mem.download(d_cd, _native.PSCL_NCOUNT * 8, np.int64)}
+
+
+def _retries_adaptive_device(dec, llr, B, W, R, K, retries, beta, msg, out) -> None:
+    nc = _native.PSCL_NCOUNT
+    with _native.DeviceArena(dec) as mem:
+        d_llr = mem.alloc(llr.nbytes)
+        mem.upload(d_llr, llr)
+        d_best = mem.alloc(B * W * 8)
+        d_flags = mem.alloc(B)
+        d_stage = mem.alloc(B)
+        d_att = mem.alloc(B * 4)
+        d_tried = mem.alloc(max(B * R * 4, 4))
+        d_n = mem.alloc(8)
+        d_ref = d_cnt = 0
+        if msg is not None:
+            d_ref = mem.alloc(B * W * 8)
+            mem.upload(d_ref, bits_to_words(msg))
+            d_cnt = mem.alloc(3 * nc * 8)
+            mem.memset(d_cnt, 0, 3 * nc * 8)
+        d_bbest = mem.alloc(B * W * 8)
+        d_bflags = mem.alloc(B)
+        dec.adaptive_async_device(d_llr, B, d_best=d_bbest, d_flags=d_bflags)
+        dec.adaptive_dlscl_device(d_llr, B, retries, beta=beta, d_best=d_best, d_flags=d_flags, d_stage=d_stage,
+                                  d_attempts=d_att, d_tried=d_tried if R else 0, tried_stride=R, d_ref=d_ref,
+                                  k_payload=K - dec.crc_deg, d_counters=d_cnt, d_n_escalated=d_n)
+        dec.sync()
+        flags = mem.download(d_flags, B, np.uint8)
+        bflags = mem.download(d_bflags, B, np.uint8)
+        out["best_bits"] = words_to_bits(mem.download(d_best, B * W * 8, np.uint64).reshape(B, W), K)
+        out["success"] = (flags & _native.PSCL_FLAG_CRC_PASS) != 0
+        out["attempts"] = mem.download(d_att, B * 4, np.int32)
+        out["tried"] = (mem.download(d_tried, B * R * 4, np.int32).reshape(B, R) if R
+                        else np.zeros((B, 0), np.int32))
+        out["stage"] = mem.download(d_stage, B, np.uint8)
+        out["n_escalated"] = int(mem.download(d_n, 8, np.int32)[0])
+        out["base_bits"] = words_to_bits(mem.download(d_bbest, B * W * 8, np.uint64).reshape(B, W), K)
+        out["base_pass"] = (bflags & _native.PSCL_FLAG_CRC_PASS) != 0
+        if msg is not None:
+            cnt = mem.download(d_cnt, 3 * nc * 8, np.int64).reshape(3, nc)
+            out["counters"] = {"sc": cnt[0].copy(), "scl": cnt[1].copy(), "dl": cnt[2].copy()}
 
 
 __all__ = ["choose_flip_index", "retry_with_flip", "decode_with_retries", "decode_with_retries_batch",
