@@ -316,6 +316,39 @@ int pscl_adaptive_async_device(pscl_handle* h, const double* d_llr, int64_t B, u
                                int32_t* d_n_escalated);
 
 /*
+ * Float32 rows.  The calls below take d_llr as [B][N] (or, on a rate-matched handle, [B][E])
+ * float32 and otherwise the arguments of their float64 forms; pscl_decode_device_f32 is the plain
+ * decode (no forced bits, metrics, candidates or decision LLRs).  Contract: every output -- d_best,
+ * d_flags, d_stage, d_n_escalated, every counter added into d_counters, the deferred-frame count of
+ * pscl_screening_count -- equals the float64 form's on the rows widened value by value
+ * ((double)row[i], which is exact: float32 subnormals and -0 keep their value and sign), on a
+ * pipelined handle too.  Rate-matched values are widened first, then summed and divided in float64;
+ * nothing is summed in float32.  d_llr needs 4-byte alignment only (rows of an odd E start on
+ * 4-byte boundaries).  Non-finite values are outside the contract, as for float64.  Whether a call's
+ * rows are float32 is a property of that call alone: float64 and float32 calls may alternate on one
+ * handle, pipelined or not.
+ *
+ * pscl_f32_available(h) is 1 where pscl_decode_device_f32, pscl_escalate_device_f32 and
+ * pscl_adaptive_async_device_f32 have native kernels, else 0 (0 for a NULL handle): N = 128, L = 4 or
+ * 8, screening on, the compiled-in (128,64) code on plain rows or the compiled-in (128,88) code on
+ * rate-matched rows, PSCL_TUNE_LANE_EXACT at its default.  Where it is 0 those three return
+ * PSCL_EUNSUP with a message that names the reason; the argument errors of the float64 forms come
+ * first, with the same codes.  pscl_sc_device_f32 is the SC stage alone and takes every N = 128
+ * handle (any information set, plain and rate-matched rows); PSCL_EUNSUP for other N.
+ */
+int pscl_f32_available(pscl_handle* h);
+int pscl_decode_device_f32(pscl_handle* h, const float* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                           const uint64_t* d_ref, int k_payload, int64_t* d_counters);
+int pscl_sc_device_f32(pscl_handle* h, const float* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                       uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters);
+int pscl_escalate_device_f32(pscl_handle* h, const float* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                             uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                             int64_t* n_escalated);
+int pscl_adaptive_async_device_f32(pscl_handle* h, const float* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                                   uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                                   int32_t* d_n_escalated);
+
+/*
  * One SNR point of a Monte-Carlo sweep with adaptive decoding, for global frames
  * [frame0, frame0 + B): pscl_channel_device (and the optional uncoded baseline) with the Philox
  * stream pscl_simulate uses -- shards add up exactly -- then the SC stage and the escalation of

@@ -47,6 +47,8 @@ EXPORTS = (
     "pscl_sc_device", "pscl_escalate_device",
     "pscl_adaptive_async_device", "pscl_simulate_adaptive", "pscl_simulate_adaptive_device", "pscl_adaptive_stats",
     "pscl_retry_device", "pscl_adaptive_dlscl_device", "pscl_simulate_adaptive_dl", "pscl_simulate_adaptive_dl_device",
+    "pscl_f32_available", "pscl_decode_device_f32", "pscl_sc_device_f32", "pscl_escalate_device_f32",
+    "pscl_adaptive_async_device_f32",
 )
 
 # pscl_set_tuning knobs (include/polar_scl.h)
@@ -121,6 +123,11 @@ def lib() -> C.CDLL:
         "pscl_decode_adaptive_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, C.c_int, _u64, _vp, _i64, _vp, _vp, _vp, _vp,
                                                C.c_int]),
         "pscl_adaptive_async_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+        "pscl_f32_available": (C.c_int, [_vp]),
+        "pscl_decode_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, C.c_int, _vp]),
+        "pscl_sc_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+        "pscl_escalate_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, P(_i64)]),
+        "pscl_adaptive_async_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp]),
         "pscl_simulate_adaptive_device": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, _vp]),
         "pscl_simulate_adaptive": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, _vp]),
         "pscl_adaptive_stats": (C.c_int, [_vp, P(_i64), P(_i64), P(_i64), C.c_int]),
@@ -408,6 +415,43 @@ class Decoder:
             check(lib().pscl_adaptive_async_device(self._h, d_llr or None, int(B), d_best or None, d_flags or None,
                                                    d_stage or None, d_ref or None, int(k_payload), d_counters or None,
                                                    d_n_escalated or None))
+
+    # ---- float32 rows: d_llr points at [B][N or E] float32; outputs equal the float64 calls' on the
+    # widened rows (include/polar_scl.h)
+    def f32_available(self) -> bool:
+        """Whether decode_device_f32, escalate_device_f32 and adaptive_async_device_f32 have native
+        kernels on this handle (pscl_f32_available); where not, they raise (PSCL_EUNSUP)."""
+        return bool(lib().pscl_f32_available(self._h))
+
+    def decode_device_f32(self, d_llr: int, B: int, *, d_best=0, d_flags=0, d_ref=0, k_payload=0, d_counters=0) -> None:
+        """The plain list decode of float32 rows (pscl_decode_device_f32)."""
+        check(lib().pscl_decode_device_f32(self._h, d_llr or None, int(B), d_best or None, d_flags or None, d_ref or None,
+                                           int(k_payload), d_counters or None))
+
+    def sc_device_f32(self, d_llr: int, B: int, *, d_best: int, d_flags: int, d_stage=0, d_ref=0, k_payload=0,
+                      d_counters=0) -> None:
+        """sc_device on float32 rows (pscl_sc_device_f32; N = 128, any information set)."""
+        with self._lock:
+            check(lib().pscl_sc_device_f32(self._h, d_llr or None, int(B), d_best or None, d_flags or None, d_stage or None,
+                                           d_ref or None, int(k_payload), d_counters or None))
+
+    def escalate_device_f32(self, d_llr: int, B: int, *, d_best: int, d_flags: int, d_stage=0, d_ref=0, k_payload=0,
+                            d_counters=0) -> int:
+        """escalate_device on float32 rows (pscl_escalate_device_f32).  Returns the escalated count."""
+        n = _i64()
+        with self._lock:
+            check(lib().pscl_escalate_device_f32(self._h, d_llr or None, int(B), d_best or None, d_flags or None,
+                                                 d_stage or None, d_ref or None, int(k_payload), d_counters or None,
+                                                 C.byref(n)))
+        return int(n.value)
+
+    def adaptive_async_device_f32(self, d_llr: int, B: int, *, d_best: int, d_flags: int, d_stage=0, d_ref=0,
+                                  k_payload=0, d_counters=0, d_n_escalated=0) -> None:
+        """adaptive_async_device on float32 rows (pscl_adaptive_async_device_f32)."""
+        with self._lock:
+            check(lib().pscl_adaptive_async_device_f32(self._h, d_llr or None, int(B), d_best or None, d_flags or None,
+                                                       d_stage or None, d_ref or None, int(k_payload),
+                                                       d_counters or None, d_n_escalated or None))
 
     def adaptive_stats(self, reset: bool = False) -> dict:
         """Paths of the adaptive calls without a host wait (pscl_adaptive_stats): stage-2 launches on

@@ -23,11 +23,17 @@ LIB = PKG / "libpolar_mi355x.so"
 ARCH = os.environ.get("PSCL_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-HIP_SOURCES = ["scl_kernels.hip", "scl128.hip", "scl128_spec.hip", "scl128_lane.hip", "scl128_lane_rl.hip", "sc128_lane.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "capi.cpp",
+HIP_SOURCES = ["scl_kernels.hip", "scl128.hip", "scl128_spec.hip", "scl128_lane.hip", "scl128_lane_rl.hip", "sc128_lane.hip",
+               "scl128_lane_f32.hip", "scl128_lane_rl_f32.hip", "sc128_lane_f32.hip", "scl128_spec_f32.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "capi.cpp",
                "scl_cpu.cpp"]
 HIP_DEPS = HIP_SOURCES + ["scl_kernels.h", "scl_device.h", "scl128_impl.h", "glibc_softplus.h", "exp_table.inc"]
 # scl128_spec.hip is compiled once per (information-set code, list size): 8 objects
 SPEC_UNITS = [(c, l) for c in (1, 2) for l in (1, 2, 4, 8)]
+# scl128_spec_f32.hip (the exact re-decode over float32 rows) likewise: 4 objects
+SPEC_F32_UNITS = [(c, l) for c in (1, 2) for l in (4, 8)]
+# units that compile another unit's source with a switch (the source is part of their content key)
+WRAPPED = {"scl128_lane_rl.hip": "scl128_lane.hip", "scl128_lane_f32.hip": "scl128_lane.hip",
+           "scl128_lane_rl_f32.hip": "scl128_lane.hip", "sc128_lane_f32.hip": "sc128_lane.hip"}
 
 
 BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result", "-Wno-unused-value"]
@@ -38,7 +44,7 @@ def source_hash(flags: list[str] | None = None) -> str:
     """sha256 (16 hex digits) of every source and header the library is compiled from, the
     target, the compile flags and the unit list.  Embedded in the library (pscl_build_hash)."""
     h = hashlib.sha256()
-    h.update(" ".join([ARCH, *BASE_FLAGS, *(flags or []), repr(SPEC_UNITS), *HIP_SOURCES]).encode())
+    h.update(" ".join([ARCH, *BASE_FLAGS, *(flags or []), repr(SPEC_UNITS), repr(SPEC_F32_UNITS), *HIP_SOURCES]).encode())
     for f in [*(CSRC / s for s in HIP_DEPS), INCLUDE / "polar_scl.h"]:
         h.update(f.name.encode() + b"\0" + f.read_bytes())
     return h.hexdigest()[:16]
@@ -64,6 +70,10 @@ def hip_units(objdir: Path, tag: str = "", hash_: str | None = None) -> list[tup
             for c, l in SPEC_UNITS:
                 units.append((CSRC / src, [f"-DPSCL_SPEC_CODE={c}", f"-DPSCL_SPEC_LMAX={l}"],
                               objdir / f"scl128_spec_{c}_{l}{tag}.o"))
+        elif src == "scl128_spec_f32.hip":
+            for c, l in SPEC_F32_UNITS:
+                units.append((CSRC / src, [f"-DPSCL_SPEC_CODE={c}", f"-DPSCL_SPEC_LMAX={l}"],
+                              objdir / f"scl128_spec_f32_{c}_{l}{tag}.o"))
         else:
             extra = [f'-DPSCL_BUILD_HASH="{hash_}"'] if (src == "capi.cpp" and hash_) else []
             units.append((CSRC / src, extra, objdir / (Path(src).stem + tag + ".o")))
@@ -105,8 +115,8 @@ def unit_key(unit, flags: list[str]) -> str:
     h = hashlib.sha256()
     h.update("\0".join([ARCH, HIPCC, *BASE_FLAGS, *unit[1], *flags]).encode())
     headers = sorted([*CSRC.glob("*.h"), *CSRC.glob("*.inc"), *INCLUDE.glob("*.h")])
-    if unit[0].name == "scl128_lane_rl.hip":  # (it compiles scl128_lane.hip with another switch)
-        headers.append(CSRC / "scl128_lane.hip")
+    if unit[0].name in WRAPPED:  # (it compiles another unit's source with a switch)
+        headers.append(CSRC / WRAPPED[unit[0].name])
     for f in [unit[0], *headers]:
         h.update(f.name.encode() + b"\0" + f.read_bytes())
     return h.hexdigest()[:32]

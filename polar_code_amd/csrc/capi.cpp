@@ -380,6 +380,27 @@ bool lane_exact_on(const pscl_handle* h) {
     return lx == 1 || lx == 3 || (lx == 0 && PSCL_LANE_EXACT_DEFAULT);
 }
 
+// float32 rows (the pscl_*_f32 entry points): why this handle's list decode has no float32 kernels, or
+// null where it has -- the handles whose plain decode is the lane-per-path screening kernel plus the
+// compiled-in exact re-decode (N = 128, L = 4 or 8, screening on, the (128,64) code on plain rows or the
+// (128,88) code on rate-matched rows, no knob that moves a launch to another instance).  The flag that
+// marks a launch's rows as float32 is per call (pscl_decode_params::f32; for the SC stage, which of the
+// two launch functions is called), never handle state: every kernel argument block is copied when its
+// launch is enqueued, so work deferred to a side stream keeps the type of its own call's rows.
+const char* f32_unsupported(const pscl_handle* h) {
+    if (h->N != PSCL_FAST_N) return "float32 rows are decoded at N = 128 only";
+    if (h->L != 4 && h->L != 8) return "float32 rows are decoded at L = 4 and 8 only";
+    if (!h->screen) return "float32 rows need the screening decode (pscl_set_screening is off)";
+    if (h->tune[PSCL_TUNE_LANE_EXACT] == 3 || lane_exact_on(h))
+        return "PSCL_TUNE_LANE_EXACT selects the exact lane-per-path instance, which has no float32 form";
+    pscl_decode_params P;
+    fill_decode_params(h, P, 0);
+    if (!pscl_f32_decode_available(P))
+        return h->rm_E ? "float32 rate-matched rows are decoded for the compiled-in (128,88) code only"
+                       : "float32 plain rows are decoded for the compiled-in (128,64) code only (runtime information set)";
+    return nullptr;
+}
+
 // tail (a pipelined DL-SCL baseline, tail_par its scratch parity): the re-decode of the deferred
 // frames goes to tail after the screening pass, and the call returns; the caller queues the rest of
 // the baseline's tail there and marks it with ev_tail[tail_par]
@@ -817,7 +838,9 @@ int pscl_sync(pscl_handle* h) {
     return PSCL_OK;
 }
 
-int pscl_decode_device(pscl_handle* h, const double* d_llr, int64_t B, const uint64_t* d_force, uint64_t* d_best,
+namespace {
+// pscl_decode_device and (f32: d_llr points at float32 rows) pscl_decode_device_f32
+int decode_device_impl(pscl_handle* h, const void* d_llr, bool f32, int64_t B, const uint64_t* d_force, uint64_t* d_best,
                        uint8_t* d_flags, double* d_metrics, uint64_t* d_cands, double* d_info_llrs,
                        const uint64_t* d_ref, int k_payload, int64_t* d_counters) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
@@ -826,12 +849,16 @@ int pscl_decode_device(pscl_handle* h, const double* d_llr, int64_t B, const uin
     if (!d_llr) return fail(PSCL_EINVAL, "d_llr is NULL");
     if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
     if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
+    if (f32) {
+        if (const char* why = f32_unsupported(h)) return fail(PSCL_EUNSUP, "%s", why);
+    }
     int rc = set_device(h);
     if (rc) return rc;
     const int hist = d_info_llrs != nullptr;
     pscl_decode_params P;
     fill_decode_params(h, P, hist);
-    P.llr = d_llr;
+    P.llr = (const double*)d_llr;  // (f32: floats; only the float32 instances take the launch)
+    P.f32 = f32 ? 1 : 0;
     P.B = B;
     P.force = d_force;
     P.best = d_best;
@@ -847,12 +874,30 @@ int pscl_decode_device(pscl_handle* h, const double* d_llr, int64_t B, const uin
     if (h->pipelined && (h->ad_pending[0] || h->ad_pending[1]) && (rc = join_pipe(h, 1))) return rc;  // (adaptive calls' stage 2)
     return launch_decode(h, P, hist, nullptr, 38, h->pipelined);
 }
+}  // namespace
+
+int pscl_decode_device(pscl_handle* h, const double* d_llr, int64_t B, const uint64_t* d_force, uint64_t* d_best,
+                       uint8_t* d_flags, double* d_metrics, uint64_t* d_cands, double* d_info_llrs,
+                       const uint64_t* d_ref, int k_payload, int64_t* d_counters) {
+    return decode_device_impl(h, d_llr, false, B, d_force, d_best, d_flags, d_metrics, d_cands, d_info_llrs, d_ref, k_payload,
+                              d_counters);
+}
+
+int pscl_decode_device_f32(pscl_handle* h, const float* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                           const uint64_t* d_ref, int k_payload, int64_t* d_counters) {
+    return decode_device_impl(h, d_llr, true, B, nullptr, d_best, d_flags, nullptr, nullptr, nullptr, d_ref, k_payload,
+                              d_counters);
+}
+
+int pscl_f32_available(pscl_handle* h) { return h && !f32_unsupported(h) ? 1 : 0; }
 
 namespace {
 
 // the SC stage over all B frames as one launch on the handle's stream (sc128_lane.hip at N = 128,
 // sc_lane.hip at the other lengths), timed like a decode when timing is on
-int launch_sc_stage(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags, uint8_t* d_stage) {
+// f32: d_llr points at float32 rows (N = 128 only; the callers check)
+int launch_sc_stage(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags, uint8_t* d_stage,
+                    bool f32 = false) {
     hipStream_t s = h->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->timing) {  // (the SC launch is one timed launch on the handle's stream, like a decode)
@@ -885,8 +930,9 @@ int launch_sc_stage(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_
         S.best = d_best;
         S.flags = d_flags;
         S.stage = d_stage;
-        e = pscl_launch_sc_lane(S, s);
+        e = f32 ? pscl_launch_sc_lane_f32(S, s) : pscl_launch_sc_lane(S, s);
     } else {
+        if (f32) return fail(PSCL_EUNSUP, "float32 rows: the SC stage takes N = %d only (N = %d)", PSCL_FAST_N, h->N);
         if (!pscl_scn_lane_available(h->N) || h->rm_E)
             return fail(PSCL_EUNSUP, "no SC kernel for N = %d%s", h->N, h->rm_E ? " with rate matching" : "");
         pscl_scn_params S;
@@ -914,8 +960,9 @@ int launch_sc_stage(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_
 // of that many frames -- the screening path, not a row list, which would land on the exact kernel --
 // and scattered back; d_stage (or null) gets 2 at those frames.  Scratch slots 72..76: count, frame
 // list, dense rows, dense best words, dense flags.  One host wait: the count sizes the dense batch.
+// f32: d_llr points at float32 rows, widened while they are gathered; the dense batch is doubles
 int escalate_failed(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags, uint8_t* d_stage,
-                    int64_t* n_out) {
+                    int64_t* n_out, bool f32 = false) {
     const int W = h->W;
     const int64_t row = h->rm_E ? h->rm_E : h->N;
     hipStream_t s = h->stream;
@@ -939,7 +986,9 @@ int escalate_failed(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_
         if ((rc = ensure(h, 74, (size_t)n * (size_t)row * 8, &d_rows))) return rc;
         if ((rc = ensure(h, 75, (size_t)n * W * 8, &d_b2))) return rc;
         if ((rc = ensure(h, 76, (size_t)n, &d_f2))) return rc;
-        if ((e = pscl_launch_gather_rows(d_llr, row, (const int64_t*)d_act, n, (double*)d_rows, s)) != hipSuccess)
+        e = f32 ? pscl_launch_gather_rows_f32((const float*)d_llr, row, (const int64_t*)d_act, n, (double*)d_rows, s)
+                : pscl_launch_gather_rows(d_llr, row, (const int64_t*)d_act, n, (double*)d_rows, s);
+        if (e != hipSuccess)
             return fail(PSCL_EDEVICE, "gather launch: %s", hipGetErrorString(e));
         pscl_decode_params P;
         fill_decode_params(h, P, 0);
@@ -998,7 +1047,8 @@ int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
     return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, n);
 }
 
-int pscl_sc_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+namespace {
+int sc_device_impl(pscl_handle* h, const double* d_llr, bool f32, int64_t B, uint64_t* d_best, uint8_t* d_flags,
                    uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
@@ -1007,15 +1057,29 @@ int pscl_sc_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_b
     if (h->N < 32) return fail(PSCL_EUNSUP, "the SC stage is implemented for N = 32 .. %d (N = %d)", PSCL_MAX_N, h->N);
     if (h->rm_E && h->N != PSCL_FAST_N)
         return fail(PSCL_EUNSUP, "the SC stage takes rate-matched rows at N = %d only (N = %d)", PSCL_FAST_N, h->N);
+    if (f32 && h->N != PSCL_FAST_N)
+        return fail(PSCL_EUNSUP, "float32 rows: the SC stage takes N = %d only (N = %d)", PSCL_FAST_N, h->N);
     if (B == 0) return PSCL_OK;
     if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
     int rc = enter(h);  // (pending pipelined work first)
     if (rc) return rc;
-    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage))) return rc;
+    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage, f32))) return rc;
     return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, 0);
 }
+}  // namespace
 
-int pscl_escalate_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+int pscl_sc_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                   uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters) {
+    return sc_device_impl(h, d_llr, false, B, d_best, d_flags, d_stage, d_ref, k_payload, d_counters);
+}
+
+int pscl_sc_device_f32(pscl_handle* h, const float* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                       uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters) {
+    return sc_device_impl(h, (const double*)d_llr, true, B, d_best, d_flags, d_stage, d_ref, k_payload, d_counters);
+}
+
+namespace {
+int escalate_device_impl(pscl_handle* h, const double* d_llr, bool f32, int64_t B, uint64_t* d_best, uint8_t* d_flags,
                          uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
                          int64_t* n_escalated) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
@@ -1027,12 +1091,29 @@ int pscl_escalate_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
     if (B == 0) return PSCL_OK;
     if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
     if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
+    if (f32) {
+        if (const char* why = f32_unsupported(h)) return fail(PSCL_EUNSUP, "%s", why);
+    }
     int rc = enter(h);
     if (rc) return rc;
     int64_t n = 0;
-    if ((rc = escalate_failed(h, d_llr, B, d_best, d_flags, d_stage, &n))) return rc;
+    if ((rc = escalate_failed(h, d_llr, B, d_best, d_flags, d_stage, &n, f32))) return rc;
     if (n_escalated) *n_escalated = n;
     return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, n);
+}
+}  // namespace
+
+int pscl_escalate_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                         uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                         int64_t* n_escalated) {
+    return escalate_device_impl(h, d_llr, false, B, d_best, d_flags, d_stage, d_ref, k_payload, d_counters, n_escalated);
+}
+
+int pscl_escalate_device_f32(pscl_handle* h, const float* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                             uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                             int64_t* n_escalated) {
+    return escalate_device_impl(h, (const double*)d_llr, true, B, d_best, d_flags, d_stage, d_ref, k_payload, d_counters,
+                                n_escalated);
 }
 
 namespace {
@@ -1072,9 +1153,11 @@ int adaptive_begin(pscl_handle* h, bool pipe, int* par) {
 // handle's plain decode has no lane-per-path screening kernel, the exact kernel on the list itself.
 // Then (d_ref) the statistics of all B final outputs, and the escalated count from device memory.
 // pipe: everything after the compaction on parity q's side stream behind ev_adc[q]; ev_ad[q] marks its end.
+// f32: d_llr points at float32 rows (a handle with float32 kernels, f32_unsupported; the callers check):
+// the row-list launch and the exact re-decode are the float32 instances
 int adaptive_escalate_enqueue(pscl_handle* h, int q, bool pipe, const double* d_llr, int64_t B, uint64_t* d_best,
                               uint8_t* d_flags, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
-                              int32_t* d_n_escalated) {
+                              int32_t* d_n_escalated, bool f32 = false) {
     hipStream_t s = h->stream;
     const int base = kAdSlot[q];
     const int64_t regrown = h->n_regrow;
@@ -1095,6 +1178,7 @@ int adaptive_escalate_enqueue(pscl_handle* h, int q, bool pipe, const double* d_
     P.fidx = (const int64_t*)d_list;
     P.d_count = esc_cnt;
     P.out_by_row = 1;
+    P.f32 = f32 ? 1 : 0;  // (S and X below inherit it)
     if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
     pscl_decode_params S = P;  // the row-list screening launch
     S.apx = 1;
@@ -1166,13 +1250,17 @@ int adaptive_async_args(pscl_handle* h, int64_t B, int k_payload) {
 
 }  // namespace
 
-int pscl_adaptive_async_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
-                               uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
-                               int32_t* d_n_escalated) {
+namespace {
+int adaptive_async_impl(pscl_handle* h, const double* d_llr, bool f32, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                        uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                        int32_t* d_n_escalated) {
     int rc = adaptive_async_args(h, B, k_payload);
     if (rc) return rc;
     if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
     if (B > 0 && (!d_llr || !d_best || !d_flags)) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
+    if (f32) {
+        if (const char* why = f32_unsupported(h)) return fail(PSCL_EUNSUP, "%s", why);
+    }
     const bool pipe = h->pipelined;
     // (pending pipelined work first; a pipelined call orders the earlier adaptive calls by parity)
     if ((rc = set_device(h)) || (rc = join_pipe(h, pipe ? 3 + 8 : 3))) return rc;
@@ -1182,8 +1270,22 @@ int pscl_adaptive_async_device(pscl_handle* h, const double* d_llr, int64_t B, u
     }
     int q = 0;
     if ((rc = adaptive_begin(h, pipe, &q))) return rc;
-    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage))) return rc;
-    return adaptive_escalate_enqueue(h, q, pipe, d_llr, B, d_best, d_flags, d_ref, k_payload, d_counters, d_n_escalated);
+    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage, f32))) return rc;
+    return adaptive_escalate_enqueue(h, q, pipe, d_llr, B, d_best, d_flags, d_ref, k_payload, d_counters, d_n_escalated, f32);
+}
+}  // namespace
+
+int pscl_adaptive_async_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                               uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                               int32_t* d_n_escalated) {
+    return adaptive_async_impl(h, d_llr, false, B, d_best, d_flags, d_stage, d_ref, k_payload, d_counters, d_n_escalated);
+}
+
+int pscl_adaptive_async_device_f32(pscl_handle* h, const float* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
+                                   uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                                   int32_t* d_n_escalated) {
+    return adaptive_async_impl(h, (const double*)d_llr, true, B, d_best, d_flags, d_stage, d_ref, k_payload, d_counters,
+                               d_n_escalated);
 }
 
 int pscl_adaptive_stats(pscl_handle* h, int64_t* screened, int64_t* exact, int64_t* host_waits, int reset) {

@@ -35,6 +35,20 @@
 
 using namespace pscl;
 
+// Float32 rows (pscl_sc_device_f32 and the SC stage of the other _f32 calls): sc128_lane_f32.hip compiles
+// this file with PSCL_SC128_F32_UNIT and gets the two kernel instances over float rows under a name of
+// their own (sc128_lane_kernel_f32<RM>), the float32 twin of the row gather, and their launches -- and
+// nothing else, so this file's own code object holds exactly what it held before.  A row element is
+// widened as it is loaded (v_cvt_f64_f32, exact; the wave's fp32 denormal mode is IEEE in every
+// instance, so subnormals and -0 keep their value and sign); everything after the load is this file's
+// fp64 code unchanged.
+#ifdef PSCL_SC128_F32_UNIT
+using sc_llr_t = float;
+#define sc128_lane_kernel sc128_lane_kernel_f32
+#else
+using sc_llr_t = double;
+#endif
+
 namespace {
 
 constexpr int kQuadX1 = 0xB1;  // quad_perm [1,0,3,2]: lane q ^ 1
@@ -70,16 +84,16 @@ __device__ __forceinline__ double flip_sign(double v, uint32_t s) {
 // nr_stage (scl_device.h) with the mean's division by a power-of-two count done as the exact
 // multiplication by its reciprocal -- the same correctly rounded value; E = 256 averages pairs, and
 // 32 fp64 divisions per lane were most of the rate-matched front end
-__device__ __forceinline__ double nr_value(const double* src, int k, int E) {
+__device__ __forceinline__ double nr_value(const sc_llr_t* src, int k, int E) {
     constexpr int N = 128;
-    if (E <= N) return k < E ? src[k] : -1.0;
+    if (E <= N) return k < E ? (double)src[k] : -1.0;
     const int reps = E / N, rem = E - reps * N;
-    double s = src[k];
-    for (int r = 1; r < reps; ++r) s = s + src[k + r * N];
+    double s = (double)src[k];
+    for (int r = 1; r < reps; ++r) s = s + (double)src[k + r * N];
     s = 0.0 + s;
     int cnt = reps;
     if (k < rem) {
-        s = s + src[reps * N + k];
+        s = s + (double)src[reps * N + k];
         ++cnt;
     }
     if ((cnt & (cnt - 1)) == 0) return s * pscl_asf64((uint64_t)(1023 - __builtin_ctz((unsigned)cnt)) << 52);
@@ -244,7 +258,7 @@ __global__ void __attribute__((amdgpu_waves_per_eu(RM ? 2 : 3))) __launch_bounds
          g0 += (int64_t)gridDim.x * kFramesPerWg) {
         const int64_t f = g0 + (lane >> 2);
         const bool valid = f < P.B;
-        const double* row = P.llr + (valid ? f : g0) * rowlen;  // (a ragged wave's empty quads decode frame g0 again)
+        const sc_llr_t* row = reinterpret_cast<const sc_llr_t*>(P.llr) + (valid ? f : g0) * rowlen;  // (a ragged wave's empty quads decode frame g0 again)
         double ch[32];
         if constexpr (RM) {
             // rate matched: position k = 4 j + q of the de-rate-matched vector is formed from its
@@ -260,8 +274,10 @@ __global__ void __attribute__((amdgpu_waves_per_eu(RM ? 2 : 3))) __launch_bounds
             for (int j = 0; j < 32; ++j) ch[j] = st[P.rm_src[4 * j + (int)q]];
             wave_lds_fence();  // (read before the next iteration's rows overwrite them)
         } else {
+            // (float32 rows: one 4-byte load per lane and slot, a quad reading 16 contiguous bytes; 8- and
+            // 16-byte loads with a quad_perm exchange measured 1-4 % slower)
 #pragma unroll
-            for (int j = 0; j < 32; ++j) ch[j] = row[4 * j + (int)q];
+            for (int j = 0; j < 32; ++j) ch[j] = (double)row[4 * j + (int)q];
         }
         uint32_t u[4] = {0u, 0u, 0u, 0u};
         // (the mask made opaque per iteration: hoisted out of the frame loop, the 255 sub-tree tests
@@ -308,6 +324,18 @@ __global__ void __attribute__((amdgpu_waves_per_eu(RM ? 2 : 3))) __launch_bounds
     }
 }
 
+#ifdef PSCL_SC128_F32_UNIT
+// rows act[i] of the float32 llr, widened, densely: one thread per value
+__global__ void __launch_bounds__(256) sc_gather_rows_f32_kernel(const float* __restrict__ llr, int64_t row,
+                                                                 const int64_t* __restrict__ act, int64_t n,
+                                                                 double* __restrict__ out) {
+    const int64_t total = n * row;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / row, k = i - r * row;
+        out[i] = (double)llr[act[r] * row + k];
+    }
+}
+#else
 // rows act[i] of llr, densely: one thread per value
 __global__ void __launch_bounds__(256) sc_gather_rows_kernel(const double* __restrict__ llr, int64_t row,
                                                              const int64_t* __restrict__ act, int64_t n,
@@ -346,7 +374,32 @@ __global__ void sc_publish_count_kernel(const int32_t* __restrict__ count, int64
     }
 }
 
+#endif  // PSCL_SC128_F32_UNIT
+
 }  // namespace
+
+#ifdef PSCL_SC128_F32_UNIT
+// (grid, workgroup and LDS as the float64 launch: the staging rows of the rate-matched form hold doubles)
+hipError_t pscl_launch_sc_lane_f32(const pscl_sc_params& P, hipStream_t s) {
+    if (P.B <= 0) return hipSuccess;
+    const dim3 g((unsigned)pscl_sc_lane_grid(P)), b(wavesPerWg(P.rm_E != 0) * 64);
+    const size_t lds = (size_t)pscl_sc_lane_lds(P);
+    if (P.rm_E)
+        hipLaunchKernelGGL(sc128_lane_kernel<true>, g, b, lds, s, P);
+    else
+        hipLaunchKernelGGL(sc128_lane_kernel<false>, g, b, lds, s, P);
+    return hipGetLastError();
+}
+
+hipError_t pscl_launch_gather_rows_f32(const float* llr, int64_t row, const int64_t* act, int64_t n, double* out,
+                                       hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    int64_t grid = (n * row + 255) / 256;
+    if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(sc_gather_rows_f32_kernel, dim3((unsigned)grid), dim3(256), 0, s, llr, row, act, n, out);
+    return hipGetLastError();
+}
+#else
 
 int pscl_sc_lane_lds(const pscl_sc_params& P) {
     return P.epi_words * 8 + (P.rm_E ? wavesPerWg(true) * kFramesPerWave * kStageStride * 8 : 0);
@@ -400,3 +453,4 @@ hipError_t pscl_launch_publish_count(const int32_t* count, int64_t* counters, in
     hipLaunchKernelGGL(sc_publish_count_kernel, dim3(1), dim3(64), 0, s, count, counters, slot, out);
     return hipGetLastError();
 }
+#endif  // PSCL_SC128_F32_UNIT

@@ -13,6 +13,13 @@ PSCL_SPEC_DECL(2, 1)
 PSCL_SPEC_DECL(2, 2)
 PSCL_SPEC_DECL(2, 4)
 PSCL_SPEC_DECL(2, 8)
+// the exact plain decodes over float32 rows (scl128_spec_f32.hip)
+#define PSCL_SPEC_F32_DECL(c, l) \
+    hipError_t pscl_launch_spec_f32_##c##_##l(const pscl_decode_params& P, int wpg, int64_t grid, int lds, hipStream_t s);
+PSCL_SPEC_F32_DECL(1, 4)
+PSCL_SPEC_F32_DECL(1, 8)
+PSCL_SPEC_F32_DECL(2, 4)
+PSCL_SPEC_F32_DECL(2, 8)
 
 namespace {
 
@@ -35,6 +42,18 @@ int spec_code(const pscl_decode_params& P) {
 template <int LMAX>
 hipError_t launch128(const pscl_decode_params& P, int hist, int wpg, int64_t grid, int lds, hipStream_t s) {
     const bool fs = P.force || P.sc_hard;
+    if (P.f32) {  // float32 rows: the exact plain decode of a compiled-in code at L = 4, 8, nothing else
+        if (hist || fs || P.apx || P.L != LMAX || P.metrics || P.cands) return hipErrorInvalidValue;
+        const int code = spec_code(P);
+        if constexpr (LMAX == 4) {
+            if (code == 1 && !P.rm_E) return pscl_launch_spec_f32_1_4(P, wpg, grid, lds, s);
+            if (code == 2 && P.rm_E) return pscl_launch_spec_f32_2_4(P, wpg, grid, lds, s);
+        } else if constexpr (LMAX == 8) {
+            if (code == 1 && !P.rm_E) return pscl_launch_spec_f32_1_8(P, wpg, grid, lds, s);
+            if (code == 2 && P.rm_E) return pscl_launch_spec_f32_2_8(P, wpg, grid, lds, s);
+        }
+        return hipErrorInvalidValue;
+    }
     if (hist)
         return P.rm_E ? launch128k<LMAX, true, true, true>(P, wpg, grid, lds, s)
                       : launch128k<LMAX, true, false, true>(P, wpg, grid, lds, s);
@@ -108,6 +127,15 @@ int pscl_lane_exact_available(const pscl_decode_params& P) {
         return code == 1 && P.elist && P.fidx && P.warm_metric && P.warm_u && !P.d_count && !P.ref && !P.rm_E && !P.out_by_row;
     if (P.elist) return 0;
     return (code == 1 && !P.rm_E) || (code == 2 && P.rm_E);
+}
+
+// a plain decode of P's shape runs on float32 rows: its screening launch is the lane-per-path kernel
+// (plain and row-list forms have float32 instances) and its exact re-decode the compiled-in scl128_kernel
+int pscl_f32_decode_available(const pscl_decode_params& P) {
+    if (PSCL_ABLATE || !PSCL_LANE || !P.fast || P.N != 128 || P.long_mode || P.no_lane || (P.L != 8 && (P.L != 4 || !PSCL_LANE4)))
+        return 0;
+    const int code = spec_code(P);
+    return (code == 1 && !P.rm_E) || (code == 2 && P.rm_E && PSCL_LANE_NR);
 }
 
 int pscl_screening_available(const pscl_decode_params& P) {

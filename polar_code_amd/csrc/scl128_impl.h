@@ -59,6 +59,17 @@ __device__ __forceinline__ void flush_counts_p(const pscl_decode_params& P, int6
 constexpr int kN = 128;
 constexpr int kn = 7;
 
+// Float32 rows (the exact re-decode of the rows a float32 screening launch defers): scl128_spec_f32.hip
+// defines PSCL_SCL128_F32 before it includes this file and gets scl128_kernel over float rows under a
+// name of its own (scl128_kernel_f32<..>): a channel value is widened where it is loaded (the in-place
+// reads of the plain form, the LDS staging store of the CH form); the rest is the fp64 code.
+#ifdef PSCL_SCL128_F32
+using llr128_t = float;
+#define scl128_kernel scl128_kernel_f32
+#else
+using llr128_t = double;
+#endif
+
 // 16-lane frames keep their 8 channel LLRs in registers across the depth-1..3 recomputes
 #ifndef PSCL_CREG
 #define PSCL_CREG 1
@@ -294,13 +305,13 @@ scl128_kernel(const pscl_decode_params P) {
             seg0 = pscl_bucket_of(f0, bpre);
         }
         const int64_t frow = P.fidx ? P.fidx[elist ? f : fsafe] : fsafe;
-        const double* chan = P.llr + frow * kN;  // !CH: channel LLRs read in place
+        const llr128_t* chan = reinterpret_cast<const llr128_t*>(P.llr) + frow * kN;  // !CH: channel LLRs read in place
         if (CH) {
             if (P.rm_E == 0) {
 #pragma unroll
-                for (int x = 0; x < kN / G; ++x) Af[g + x * G] = chan[g + x * G];
+                for (int x = 0; x < kN / G; ++x) Af[g + x * G] = (double)chan[g + x * G];
             } else {  // NR: de-rate-match + de-interleave while staging
-                const double* src = P.llr + frow * P.rm_E;
+                const llr128_t* src = reinterpret_cast<const llr128_t*>(P.llr) + frow * P.rm_E;
                 for (int x = 0; x < kN / G; ++x) Af[g + x * G] = nr_stage(src, P.rm_src[g + x * G], P.rm_E, kN);
             }
         }
@@ -312,7 +323,7 @@ scl128_kernel(const pscl_decode_params P) {
         if constexpr (CREG) {
             if (CH) wave_lds_fence();
 #pragma unroll
-            for (int m = 0; m < 8; ++m) creg[m] = CH ? Af[g + 16 * m] : chan[g + 16 * m];
+            for (int m = 0; m < 8; ++m) creg[m] = CH ? Af[g + 16 * m] : (double)chan[g + 16 * m];
         }
         uint64_t fm0 = 0, fm1 = 0, fv0 = 0, fv1 = 0;
         if (FS && force && fvalid) {
@@ -457,7 +468,7 @@ scl128_kernel(const pscl_decode_params P) {
 #pragma unroll
                     for (int m = 0; m < 8; ++m) {
                         if constexpr (CREG) c[m] = creg[m];  // (G == 16: e == g)
-                        else c[m] = CH ? Af[e + 16 * m] : chan[e + 16 * m];
+                        else c[m] = CH ? Af[e + 16 * m] : (double)chan[e + 16 * m];
                     }
                     if constexpr (kTailNC && !CREG) {  // (the check above, at phase 0)
                         if (phi == 0) {

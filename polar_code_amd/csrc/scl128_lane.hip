@@ -49,6 +49,19 @@
 #endif
 #include "scl_lane.h"
 
+// Float32 rows (pscl_decode_device_f32, stage 2 of pscl_adaptive_async_device_f32): scl128_lane_f32.hip
+// and scl128_lane_rl_f32.hip compile this file with PSCL_LANE_F32_UNIT (the latter with PSCL_LANE_RL_UNIT
+// too) and get the plain and the row-list instances over float rows, under a name of their own
+// (scl_lane_kernel_f32<..>), and their launches.  The one difference is the load site (chan / chan_at
+// and nr_stage's float overload): a value is widened as it is loaded, exactly, and the rest is this
+// file's fp64 code.  The float64 code objects hold exactly what they held before.
+#ifdef PSCL_LANE_F32_UNIT
+using lane_llr_t = float;
+#define scl_lane_kernel scl_lane_kernel_f32
+#else
+using lane_llr_t = double;
+#endif
+
 namespace {
 
 // depths 5 and 6 (4 + 2 values per path) in the registers of the path's lane, carried along when a
@@ -307,8 +320,9 @@ scl_lane_kernel(const pscl_decode_params P) {
         // CODE = 2 (the NR (128,88) code, config 5): the input rows are rate matched -- E received
         // LLRs, de-rate-matched and de-interleaved per position as the values are loaded
         constexpr bool RM = CODE == 2;
-        const double* chan = P.llr + frow * (RM ? (int64_t)P.rm_E : (int64_t)kN);
-        auto chan_at = [&](int i) -> double { return RM ? nr_stage(chan, P.rm_src[i], P.rm_E, kN) : chan[i]; };
+        // (lane_llr_t: double, or float in the float32-row units -- each value widened as it is loaded)
+        const lane_llr_t* chan = reinterpret_cast<const lane_llr_t*>(P.llr) + frow * (RM ? (int64_t)P.rm_E : (int64_t)kN);
+        auto chan_at = [&](int i) -> double { return RM ? nr_stage(chan, P.rm_src[i], P.rm_E, kN) : (double)chan[i]; };
         // the frame's channel LLRs in registers: the lane's depth-3 elements e_k = p + G k (k < EPL)
         // need c[8 k + m] = chan[e_k + 16 m] -- the same at all 8 depth-1..3 recomputes
         // (CREG = false, an L = 4 build option: the 32 values are re-read from the L2-resident row at
@@ -1317,10 +1331,17 @@ scl_lane_kernel(const pscl_decode_params P) {
 #ifdef PSCL_LANE_RL_UNIT
 // the row-list instances of the plain screening decode (pscl_rowlist(P): stage 2 of
 // pscl_adaptive_async_device); the plain launch's LDS
-hipError_t pscl_launch_lane_rowlist(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
+// (PSCL_LANE_F32_UNIT: the same over float32 rows, pscl_launch_lane_rowlist_f32; a launch whose rows are
+// of the other type is refused)
+#ifdef PSCL_LANE_F32_UNIT
+#define PSCL_LANE_RL_LAUNCH pscl_launch_lane_rowlist_f32
+#else
+#define PSCL_LANE_RL_LAUNCH pscl_launch_lane_rowlist
+#endif
+hipError_t PSCL_LANE_RL_LAUNCH(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
     const int lds8 = LaneLayout<8>::F * LaneLayout<8>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD,
               lds4 = LaneLayout<4>::F * LaneLayout<4>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD;
-    if (!pscl_rowlist(P)) return hipErrorInvalidValue;
+    if (!pscl_rowlist(P) || (P.f32 != 0) != (sizeof(lane_llr_t) == 4)) return hipErrorInvalidValue;
     const dim3 g((unsigned)grid), b(64);
     if (P.L == 8 && !P.rm_E)
         hipLaunchKernelGGL((scl_lane_kernel<8, 1, false, false, false, false, true>), g, b, lds8, s, P);
@@ -1330,6 +1351,25 @@ hipError_t pscl_launch_lane_rowlist(const pscl_decode_params& P, int64_t grid, h
         hipLaunchKernelGGL((scl_lane_kernel<4, 1, false, false, false, false, true>), g, b, lds4, s, P);
     else if (P.L == 4)
         hipLaunchKernelGGL((scl_lane_kernel<4, 2, false, false, false, false, true>), g, b, lds4, s, P);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+#elif defined(PSCL_LANE_F32_UNIT)
+// the plain instances over float32 rows (pscl_launch_lane's launches; no fused TX form)
+hipError_t pscl_launch_lane_f32(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
+    const int lds8 = LaneLayout<8>::F * LaneLayout<8>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD,
+              lds4 = LaneLayout<4>::F * LaneLayout<4>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD;
+    if (!P.f32 || P.tx) return hipErrorInvalidValue;
+    if (pscl_rowlist(P)) return pscl_launch_lane_rowlist_f32(P, grid, s);  // (scl128_lane_rl_f32.hip)
+    if (P.L == 8 && !P.rm_E)
+        hipLaunchKernelGGL((scl_lane_kernel<8, 1>), dim3((unsigned)grid), dim3(64), lds8, s, P);
+    else if (P.L == 8)
+        hipLaunchKernelGGL((scl_lane_kernel<8, 2>), dim3((unsigned)grid), dim3(64), lds8, s, P);
+    else if (P.L == 4 && !P.rm_E)
+        hipLaunchKernelGGL((scl_lane_kernel<4, 1>), dim3((unsigned)grid), dim3(64), lds4, s, P);
+    else if (P.L == 4)
+        hipLaunchKernelGGL((scl_lane_kernel<4, 2>), dim3((unsigned)grid), dim3(64), lds4, s, P);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
@@ -1344,6 +1384,7 @@ hipError_t pscl_launch_lane(const pscl_decode_params& P, int64_t grid, hipStream
     // (pscl_lane_available: the (128,64) code on plain rows, or the rate-matched NR (128,88) code)
     const int lds8 = LaneLayout<8>::F * LaneLayout<8>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD,
               lds4 = LaneLayout<4>::F * LaneLayout<4>::FSTRIDE * 8 + PSCL_LANE_LDS_PAD;
+    if (P.f32) return hipErrorInvalidValue;  // (float32 rows: pscl_launch_lane_f32)
     if (pscl_rowlist(P)) return pscl_launch_lane_rowlist(P, grid, s);  // (scl128_lane_rl.hip)
     if (P.tx) {  // the fused TX instance (plain rows of the (128,64) code, pscl_simulate_device)
         if (P.rm_E) return hipErrorInvalidValue;
@@ -1379,6 +1420,7 @@ int64_t pscl_lane_exact_grid(const pscl_decode_params& P) {
 hipError_t pscl_launch_lane_exact(const pscl_decode_params& P, hipStream_t s) {
     const int64_t grid = pscl_lane_exact_grid(P);
     const int lds8 = LaneLayout<8>::F * LaneLayout<8>::FSTRIDE_EX * 8, lds4 = LaneLayout<4>::F * LaneLayout<4>::FSTRIDE_EX * 8;
+    if (P.f32) return hipErrorInvalidValue;  // (no float32 form)
     const dim3 g((unsigned)grid), b(64);
     if (P.force) {
         if (P.L == 8)
@@ -1407,6 +1449,7 @@ hipError_t pscl_launch_lane_exact(const pscl_decode_params& P, hipStream_t s) {
 hipError_t pscl_launch_lane_fs(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
     const int lds8 = LaneLayout<8>::F * (P.fpost ? LaneLayout<8>::FSTRIDE_FS : LaneLayout<8>::FSTRIDE) * 8,
               lds4 = LaneLayout<4>::F * (P.fpost ? LaneLayout<4>::FSTRIDE_FS : LaneLayout<4>::FSTRIDE) * 8;
+    if (P.f32) return hipErrorInvalidValue;  // (no float32 form)
     if (P.fpost && (P.K != 64 || (P.fp.beta && !P.fp_beta32g))) return hipErrorInvalidValue;
     if (P.L == 8)
         if (P.fpost)

@@ -435,6 +435,21 @@ __device__ __forceinline__ double nr_stage(const double* src, int k, int E, int 
     }
     return s / (double)cnt;
 }
+// the same from float32 received values: each one widened first (exact), the sums and the division
+// in fp64 as above -- nr_stage of the widened row, never a float32 sum
+__device__ __forceinline__ double nr_stage(const float* src, int k, int E, int N) {
+    if (E <= N) return k < E ? (double)src[k] : -1.0;
+    const int reps = E / N, rem = E - reps * N;
+    double s = (double)src[k];
+    for (int r = 1; r < reps; ++r) s = s + (double)src[k + r * N];
+    s = 0.0 + s;
+    int cnt = reps;
+    if (k < rem) {
+        s = s + (double)src[reps * N + k];
+        ++cnt;
+    }
+    return s / (double)cnt;
+}
 
 // error counters of one decoded frame (run_fer_sweep.py:91-109, run_ber_sweep.py:77-82,156)
 // value of lane - 1 within each 16-lane row (row_shr:1; lane 0 of a row reads 0)

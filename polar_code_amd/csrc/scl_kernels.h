@@ -3,6 +3,7 @@
 #define PSCL_SCL_KERNELS_H
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "polar_scl.h"
@@ -81,6 +82,13 @@ struct pscl_decode_params {
     const int64_t* fidx;         // [B] or null: frame b reads LLR row fidx[b] (outputs stay at b)
     const int32_t* d_count;      // or null: decode min(B, *d_count) frames (grid sized for B)
     int rm_E;                    // NR rate matching: received length E (0 = none; llr is [B][E])
+    // 1: llr points at float32 rows ([B][N] or [B][E] floats; the pscl_*_f32 entry points set it per
+    // call): only the float32 instances may take the launch (pscl_launch_decode; scl128_lane_f32.hip,
+    // scl128_lane_rl_f32.hip, scl128_spec_f32.hip), every other kernel is refused.  It sits in what was
+    // the padding between rm_E and rm_src: no member moves and the block keeps its size, so the
+    // kernels' argument offsets -- the hidden launch arguments behind the block among them -- and with
+    // them the float64 instances' code stay as they were (static_assert below).
+    int f32;
     const int32_t* rm_src;       // [N] de-interleave source index k(i) into the de-rate-matched vector
     const uint64_t* ref;         // [B][W] or null
     int k_payload;
@@ -160,6 +168,9 @@ struct pscl_decode_params {
     // the entries it defers go to bucket 0 of the side list (their exact decode starts at phase 0)
     int warm_apx;
 };
+
+static_assert(offsetof(pscl_decode_params, rm_src) == offsetof(pscl_decode_params, rm_E) + 8,
+              "f32 fills the padding behind rm_E");
 
 #define PSCL_DL_NSEG 8     // 16-phase segments of N = 128: warm-start buckets
 #define PSCL_DL_CSTRIDE 16 // int32 stride of the bucket counters (one 64-byte line each)
@@ -266,6 +277,13 @@ struct pscl_sc_params {
 int pscl_sc_lane_lds(const pscl_sc_params& P);
 int64_t pscl_sc_lane_grid(const pscl_sc_params& P);
 hipError_t pscl_launch_sc_lane(const pscl_sc_params& P, hipStream_t s);
+// the float32-row instances (sc128_lane_f32.hip): P.llr points at floats.  (The block has no padding
+// to hold a flag, and a member more would move the hidden launch arguments behind it and so change the
+// float64 kernels' code: the row type of an SC launch is which of the two launches the caller makes.)
+hipError_t pscl_launch_sc_lane_f32(const pscl_sc_params& P, hipStream_t s);
+// pscl_launch_gather_rows from float32 rows, widened while gathered (the dense rows are doubles)
+hipError_t pscl_launch_gather_rows_f32(const float* llr, int64_t row, const int64_t* act, int64_t n, double* out,
+                                       hipStream_t s);
 // the hand-off of pscl_adaptive_device: rows act[i] (i < n) of llr gathered densely, and the dense
 // results scattered back to rows act[i]; counters[PSCL_CNT_ESCALATED] += n
 hipError_t pscl_launch_gather_rows(const double* llr, int64_t row, const int64_t* act, int64_t n, double* out,
@@ -337,6 +355,12 @@ int pscl_lane_available(const pscl_decode_params& P);
 int pscl_lane_frames_per_wg(int L);
 hipError_t pscl_launch_lane(const pscl_decode_params& P, int64_t grid, hipStream_t s);
 hipError_t pscl_launch_lane_rowlist(const pscl_decode_params& P, int64_t grid, hipStream_t s);  // scl128_lane_rl.hip
+// the float32-row forms of the two (P.f32; scl128_lane_f32.hip, scl128_lane_rl_f32.hip) and of the exact
+// re-decode of the deferred rows (scl128_spec_f32.hip: the compiled-in codes at L = 4, 8, plain decodes)
+hipError_t pscl_launch_lane_f32(const pscl_decode_params& P, int64_t grid, hipStream_t s);
+hipError_t pscl_launch_lane_rowlist_f32(const pscl_decode_params& P, int64_t grid, hipStream_t s);
+// 1: every launch of a plain decode of P's shape (screening, row list, exact re-decode) has a float32 form
+int pscl_f32_decode_available(const pscl_decode_params& P);
 // workgroups of a decode that adds its error counts with atomics (P.ref without P.cpart): each
 // wavefront strides over frames and adds its counts once at the end (lane-per-path kernels; the
 // two-lanes-per-path kernels' workgroups hold up to PSCL_MAX_WAVES_PER_WG wavefronts)

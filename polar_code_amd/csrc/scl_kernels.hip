@@ -604,6 +604,9 @@ static bool lane_long128(const pscl_decode_params& P) {
 int pscl_lane_long128_available(const pscl_decode_params& P) { return lane_long128(P) ? 1 : 0; }
 
 hipError_t pscl_launch_decode(const pscl_decode_params& P, int hist, hipStream_t s) {
+    // float32 rows (P.f32): the lane-per-path screening launch (plain or row list) and the exact
+    // compiled-in decode (pscl_launch_decode128) have float32 instances; every other kernel reads doubles
+    if (P.f32 && (hist || P.long_mode || !P.fast || !pscl_f32_decode_available(P))) return hipErrorInvalidValue;
     if (P.long_mode) {
         if (!hist && P.apx) return pscl_launch_lane_long(P, s);  // (screening: lane-per-path only)
         return pscl_launch_long(P, hist, s);
@@ -615,8 +618,10 @@ hipError_t pscl_launch_decode(const pscl_decode_params& P, int hist, hipStream_t
         // frames' counts with one atomic per counter when it ends)
         int64_t cap = P.ref && !P.cpart ? PSCL_LANE_COUNT_GRID : (1 << 20);
         if (P.grid_cap > 0 && P.grid_cap < cap) cap = P.grid_cap;  // (a row-list launch: resident workgroups)
-        return pscl_launch_lane(P, g < 1 ? 1 : (g > cap ? cap : g), s);
+        return P.f32 ? pscl_launch_lane_f32(P, g < 1 ? 1 : (g > cap ? cap : g), s)
+                     : pscl_launch_lane(P, g < 1 ? 1 : (g > cap ? cap : g), s);
     }
+    if (P.f32 && (P.apx || P.force || P.lane_exact)) return hipErrorInvalidValue;  // (the exact plain decode is what is left)
     if (!hist && pscl_lane_fs_available(P)) {  // (P.B: the round's entry capacity)
         const int fw = pscl_lane_frames_per_wg(P.L);
         const int64_t g = (P.B + fw - 1) / fw;

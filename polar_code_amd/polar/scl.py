@@ -93,25 +93,51 @@ class SCLDecoder:
         out["bits"] = out.pop("best_bits")
         return {k: v for k, v in out.items() if v is not None}
 
-    def decode_tensor(self, llr, forced_words=None, ref_words=None, k_payload: int = 0, counters=None):
-        """Device path: llr is a contiguous float64 torch tensor [B, N] on this GPU.
-        Returns (best_words [B, W] int64, flags [B] uint8) tensors; when ref_words is given,
-        error statistics are added into `counters` (int64[8] tensor)."""
+    @staticmethod
+    def _f32_rows(llr, row: int) -> bool:
+        """Validate llr for the tensor methods -- a contiguous [B, row] tensor of float64 or float32;
+        anything else raises ValueError before any device call -- and say whether it is float32."""
         import torch
 
-        if llr.dtype != torch.float64 or not llr.is_contiguous() or llr.dim() != 2 or llr.shape[1] != self.N:
-            raise ValueError("llr must be a contiguous float64 [B, N] tensor")
+        if llr.dtype not in (torch.float64, torch.float32) or not llr.is_contiguous() or llr.dim() != 2 or llr.shape[1] != row:
+            raise ValueError("llr must be a contiguous float64 or float32 [B, N] tensor")
+        return llr.dtype == torch.float32
+
+    def decode_tensor(self, llr, forced_words=None, ref_words=None, k_payload: int = 0, counters=None):
+        """Device path: llr is a contiguous float64 or float32 torch tensor [B, N] on this GPU.
+        Returns (best_words [B, W] int64, flags [B] uint8) tensors; when ref_words is given,
+        error statistics are added into `counters` (int64[8] tensor).
+
+        float32 rows take the native float32 decode (pscl_decode_device_f32) where the handle has
+        one (native.f32_available(): N = 128, L = 4 or 8, screening on, a compiled-in code) and no
+        forced bits are given; elsewhere they are widened with llr.double() and take the float64
+        call.  Either way the result is the float64 result on the widened rows.  (The widened copy
+        is a temporary of this call: on a pipelined handle the fallback joins the side-stream work
+        back into the stream before it returns, so nothing reads the copy after torch frees it.)"""
+        import torch
+
+        f32 = self._f32_rows(llr, self.N)
         B = llr.shape[0]
         W = self._dec.W
         best = torch.empty((B, W), dtype=torch.int64, device=llr.device)
         flags = torch.empty((B,), dtype=torch.uint8, device=llr.device)
         self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
+        if f32 and forced_words is None and self._dec.f32_available():
+            self._dec.decode_device_f32(
+                llr.data_ptr(), B, d_best=best.data_ptr(), d_flags=flags.data_ptr(),
+                d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
+                d_counters=counters.data_ptr() if counters is not None else 0)
+            return best, flags
+        if f32:
+            llr = llr.double()
         self._dec.decode_device(
             llr.data_ptr(), B,
             d_force=forced_words.data_ptr() if forced_words is not None else 0,
             d_best=best.data_ptr(), d_flags=flags.data_ptr(),
             d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
             d_counters=counters.data_ptr() if counters is not None else 0)
+        if f32:
+            self._dec.join()  # (the widened temporary: see above)
         return best, flags
 
     def decode_adaptive(self, llr: np.ndarray) -> dict:
@@ -149,12 +175,16 @@ class SCLDecoder:
         everything is enqueued on the caller's current torch stream and the call returns.  Returns
         (best_words [B, W] int64, flags [B] uint8, stage [B] uint8, n_escalated [1] int32) tensors;
         with ref_words the final outputs' error statistics and the escalated count are added into
-        `counters` (int64[8] tensor)."""
+        `counters` (int64[8] tensor).  float32 rows: pscl_adaptive_async_device_f32 where
+        native.f32_available(), else widened with llr.double() (see decode_tensor)."""
         import torch
 
-        row = self._dec.E or self.N
-        if llr.dtype != torch.float64 or not llr.is_contiguous() or llr.dim() != 2 or llr.shape[1] != row:
-            raise ValueError("llr must be a contiguous float64 [B, N] tensor")
+        f32 = self._f32_rows(llr, self._dec.E or self.N)
+        call = self._dec.adaptive_async_device
+        if f32 and self._dec.f32_available():
+            call = self._dec.adaptive_async_device_f32
+        elif f32:
+            llr = llr.double()
         B = llr.shape[0]
         W = self._dec.W
         best = torch.empty((B, W), dtype=torch.int64, device=llr.device)
@@ -162,16 +192,40 @@ class SCLDecoder:
         stage = torch.empty((B,), dtype=torch.uint8, device=llr.device)
         n_esc = torch.empty((1,), dtype=torch.int32, device=llr.device)
         self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
-        self._dec.adaptive_async_device(
+        call(
             llr.data_ptr(), B, d_best=best.data_ptr(), d_flags=flags.data_ptr(), d_stage=stage.data_ptr(),
             d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
             d_counters=counters.data_ptr() if counters is not None else 0, d_n_escalated=n_esc.data_ptr())
+        if f32 and call == self._dec.adaptive_async_device:
+            self._dec.join()  # (the widened temporary: see decode_tensor)
         return best, flags, stage, n_esc
 
     def decode_sc(self, llr: np.ndarray):
         """sc_decode + check_crc on every frame (pscl_sc_device, N = 32 .. 1024): (bits [B, K] int8,
         crc_pass [B] bool)."""
         return self._dec.decode_sc(llr)
+
+    def decode_tensor_sc(self, llr, ref_words=None, k_payload: int = 0, counters=None):
+        """Device path of decode_sc on the caller's current torch stream, without a host wait: returns
+        (best_words [B, W] int64, flags [B] uint8, stage [B] uint8) tensors.  float32 rows:
+        pscl_sc_device_f32 at N = 128 (any information set), else widened with llr.double()."""
+        import torch
+
+        f32 = self._f32_rows(llr, self._dec.E or self.N)
+        sc = self._dec.sc_device
+        if f32 and self.N == 128:
+            sc = self._dec.sc_device_f32
+        elif f32:
+            llr = llr.double()
+        B = llr.shape[0]
+        best = torch.empty((B, self._dec.W), dtype=torch.int64, device=llr.device)
+        flags = torch.empty((B,), dtype=torch.uint8, device=llr.device)
+        stage = torch.empty((B,), dtype=torch.uint8, device=llr.device)
+        self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
+        sc(llr.data_ptr(), B, d_best=best.data_ptr(), d_flags=flags.data_ptr(), d_stage=stage.data_ptr(),
+           d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
+           d_counters=counters.data_ptr() if counters is not None else 0)
+        return best, flags, stage
 
     def decode_staged(self, llr: np.ndarray) -> dict:
         """decode_adaptive's result at any N >= 32, as the SC stage followed by the escalation
@@ -182,12 +236,17 @@ class SCLDecoder:
 
     def decode_tensor_staged(self, llr, ref_words=None, k_payload: int = 0, counters=None):
         """Device path of decode_staged on the caller's current torch stream: returns
-        decode_tensor_adaptive's tensors.  The call waits once on the host, inside the escalation."""
+        decode_tensor_adaptive's tensors.  The call waits once on the host, inside the escalation.
+        float32 rows: pscl_sc_device_f32 and pscl_escalate_device_f32 where native.f32_available(),
+        else widened with llr.double() (see decode_tensor)."""
         import torch
 
-        row = self._dec.E or self.N
-        if llr.dtype != torch.float64 or not llr.is_contiguous() or llr.dim() != 2 or llr.shape[1] != row:
-            raise ValueError("llr must be a contiguous float64 [B, N] tensor")
+        f32 = self._f32_rows(llr, self._dec.E or self.N)
+        sc, esc = self._dec.sc_device, self._dec.escalate_device
+        if f32 and self._dec.f32_available():
+            sc, esc = self._dec.sc_device_f32, self._dec.escalate_device_f32
+        elif f32:
+            llr = llr.double()
         B = llr.shape[0]
         W = self._dec.W
         best = torch.empty((B, W), dtype=torch.int64, device=llr.device)
@@ -195,8 +254,8 @@ class SCLDecoder:
         stage = torch.empty((B,), dtype=torch.uint8, device=llr.device)
         self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
         out = dict(d_best=best.data_ptr(), d_flags=flags.data_ptr(), d_stage=stage.data_ptr())
-        self._dec.sc_device(llr.data_ptr(), B, **out)
-        self._dec.escalate_device(
+        sc(llr.data_ptr(), B, **out)
+        esc(
             llr.data_ptr(), B, **out, d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
             d_counters=counters.data_ptr() if counters is not None else 0)
         return best, flags, stage
