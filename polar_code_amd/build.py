@@ -26,7 +26,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_SOURCES = ["scl_kernels.hip", "scl128.hip", "scl128_spec.hip", "scl128_lane.hip", "scl128_lane_rl.hip", "sc128_lane.hip",
                "scl128_lane_f32.hip", "scl128_lane_rl_f32.hip", "sc128_lane_f32.hip", "scl128_spec_f32.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "capi.cpp",
                "scl_cpu.cpp"]
-HIP_DEPS = HIP_SOURCES + ["scl_kernels.h", "scl_device.h", "scl128_impl.h", "glibc_softplus.h", "exp_table.inc"]
+HIP_DEPS = HIP_SOURCES + ["scl_kernels.h", "scl_device.h", "scl128_impl.h", "scl_lane.h", "glibc_softplus.h", "exp_table.inc"]
 # scl128_spec.hip is compiled once per (information-set code, list size): 8 objects
 SPEC_UNITS = [(c, l) for c in (1, 2) for l in (1, 2, 4, 8)]
 # scl128_spec_f32.hip (the exact re-decode over float32 rows) likewise: 4 objects

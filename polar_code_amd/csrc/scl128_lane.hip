@@ -848,9 +848,17 @@ scl_lane_kernel(const pscl_decode_params P) {
                     // rank the 2L children of each frame (select_survivors), then certify: exactly L
                     // survivors, and the largest survivor (raised by the margin) below the smallest
                     // non-survivor
+                    // (select_survivors' rule, scl_lane.h, with its two frame sums read off the lane masks
+                    // the pull needs anyway: f8 = the lanes whose better child is dropped, so d =
+                    // popcount(f8); w8 = the lanes whose worse child wins)
                     const uint32_t kg = hiw(mg);
-                    bool keep_g, win_b;
-                    select_survivors<G, LMAX>(kg, kb, keep_g, win_b);
+                    uint32_t rg, rbb;
+                    rank_children<G>(kg, kb, rg, rbb);
+                    const bool keep_g = rg < (uint32_t)LMAX;
+                    const uint32_t f8 = frame_bits(wmask(!keep_g));
+                    const uint32_t d = __builtin_popcount(f8);
+                    const bool win_b = rbb < d;
+                    const uint32_t w8 = frame_bits(wmask(win_b));
 #if defined(PSCL_STATS) && PSCL_STATS == 2  // diagnostic: ranked-tier frames by surviving worse children
                     {                        // [16 + d] and near-worse count [25 + nb]; waves by max d [34 + d]
                         const uint32_t dw = frame_sum<G>(win_b ? 1u : 0u);
@@ -869,32 +877,35 @@ scl_lane_kernel(const pscl_decode_params P) {
                     const uint32_t kbu = hiw_up(mb);
                     const uint32_t su = keep_g ? (win_b ? kbu : kgu) : (win_b ? kbu : 0u);
                     const uint32_t nm = keep_g ? (win_b ? 0xffffffffu : kb) : kg;
-                    const uint32_t nsurv = frame_sum<G>((keep_g ? 1u : 0u) + (win_b ? 1u : 0u));
                     const uint32_t smax = frame_max<G>(su), nmin = frame_min<G>(nm);
-                    amb |= wmask(!(nsurv == (uint32_t)LMAX && nmin > smax)) & vmask;
+                    // exactly L survivors: the frame keeps L - d better children and popcount(w8)
+                    // worse ones, so survivors == L iff popcount(w8) == d = popcount(f8) (the sum of
+                    // keep_g + win_b over the frame's lanes, which this replaces, is that count)
+                    amb |= wmask(!((uint32_t)__builtin_popcount(w8) == d && nmin > smax)) & vmask;
                     // freed lanes take the surviving worse children: the j-th freed lane of a frame
                     // pulls the j-th winner (both counted in lane order)
-                    const uint32_t f8 = frame_bits(wmask(!keep_g)), w8 = frame_bits(wmask(win_b));
                     const uint32_t j = __builtin_popcount(f8 & ((1u << p) - 1u));
                     src = lane_of(nth_set_bit8(w8, j));
                     pull = !keep_g;
                 }
-                // the pull: metric, bits and slot table of the source lane's worse child, whose bit
-                // rides on the table word
-                const uint32_t tw = tab | ((gbit ^ 1u) << 31);
-                const uint64_t pmb = shfl_u64(pscl_asu64(mb), src);
-                const uint64_t pu0 = shfl_u64(u0, src);
-                const uint64_t pu1 = phi >= 64 ? shfl_u64(u1, src) : 0ULL;
-                const uint32_t ptw = bperm32(tw, src);
+                // the pull: bits, slot table and depth-5 / 6 registers of the source lane's path, in
+                // one exchange.  A lane that does not pull reads ITSELF (a ds_bpermute from the lane's
+                // own index returns its own value), so what a path carries needs no select -- and such
+                // a lane never reads through a src it has no use for (a keeper's j can lie past the
+                // winners).  Only the metric and the decided bit differ: a puller takes the source's
+                // WORSE child (metric mb; its bit rides on the table word), a keeper its own BETTER one.
+                const int srce = pull ? src : lane;
+                const uint64_t pmb = shfl_u64(pscl_asu64(mb), srce);
+                const uint32_t ptw = bperm32(tab | ((gbit ^ 1u) << 31), srce);
+                u0 = shfl_u64(u0, srce);
+                if constexpr (phi >= 64) u1 = shfl_u64(u1, srce);
+                tab = ptw & 0x7fffffffu;
                 double q5[4], q6[2];
-                carry(src, q5, q6);
+                carry(srce, q5, q6);
+                take(q5, q6);
                 if (pull) {
                     metric = pscl_asf64(pmb);
-                    u0 = pu0;
-                    u1 = pu1;
-                    tab = ptw & 0x7fffffffu;
                     b = ptw >> 31;
-                    take(q5, q6);
                 }
             }
             if (phi < 64) u0 |= (uint64_t)b << phi; else u1 |= (uint64_t)b << (phi - 64);

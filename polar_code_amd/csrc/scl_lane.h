@@ -205,6 +205,59 @@ __device__ __forceinline__ void select_survivors(uint32_t kg, uint32_t kb, bool&
 #endif
 }
 
+// The rank counts of select_survivors (PSCL_LANE_RANK3 form) for frames of 4 or 8 lanes, as ONE asm
+// statement: rg = #{children of the frame's other lanes below kg}, rbb = #{their worse children below
+// kb}.  Inline asm is not hazard-checked, and the DPP-read hazard exists only after a VALU write of a
+// register a DPP operand reads: kg / kb are written before the statement (one s_nop 1 waits that out),
+// and the mirrored keys mkg / mkb (G = 8: the frame's other quad) are written by the statement's own
+// second and third instructions, 18 instructions before their first DPP read -- so one wait serves
+// all seven permutations (rank3 waits once per permutation).  Nothing else writes a key register
+// inside the statement.  The caller forms keep_g, d and win_b (scl128_lane.hip, the plain tier code).
+#define PSCL_RANK3_BLK(OG, OB, QP)                                                                  \
+    "v_sub_co_u32_dpp %[t], vcc, " OG ", %[kg] quad_perm:" QP " row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_addc_co_u32 %[rg], vcc, 0, %[rg], vcc\n\t"                                                         \
+    "v_sub_co_u32_dpp %[t], vcc, " OB ", %[kg] quad_perm:" QP " row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_addc_co_u32 %[rg], vcc, 0, %[rg], vcc\n\t"                                                         \
+    "v_sub_co_u32_dpp %[t], vcc, " OB ", %[kb] quad_perm:" QP " row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_addc_co_u32 %[rbb], vcc, 0, %[rbb], vcc\n\t"
+#if PSCL_LANE_FRAME_MIRROR == 0x140
+#define PSCL_FRAME_MIRROR_DPP "row_mirror"
+#else
+#define PSCL_FRAME_MIRROR_DPP "row_half_mirror"
+#endif
+template <int G>
+__device__ __forceinline__ void rank_children(uint32_t kg, uint32_t kb, uint32_t& rg, uint32_t& rbb) {
+    static_assert(G == 4 || G == 8, "the fused rank counts are built for frames of 4 or 8 lanes");
+    uint32_t t;
+    rg = 0;
+    rbb = 0;
+    if constexpr (G == 4) {
+        asm volatile("s_nop 1\n\t"
+                     PSCL_RANK3_BLK("%[kg]", "%[kb]", "[1,0,3,2]")
+                     PSCL_RANK3_BLK("%[kg]", "%[kb]", "[2,3,0,1]")
+                     PSCL_RANK3_BLK("%[kg]", "%[kb]", "[3,2,1,0]")
+                     : [t] "=&v"(t), [rg] "+v"(rg), [rbb] "+v"(rbb)
+                     : [kg] "v"(kg), [kb] "v"(kb)
+                     : "vcc");
+    } else {
+        uint32_t mkg, mkb;
+        asm volatile("s_nop 1\n\t"
+                     "v_mov_b32_dpp %[mkg], %[kg] " PSCL_FRAME_MIRROR_DPP " row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %[mkb], %[kb] " PSCL_FRAME_MIRROR_DPP " row_mask:0xf bank_mask:0xf\n\t"
+                     PSCL_RANK3_BLK("%[kg]", "%[kb]", "[1,0,3,2]")
+                     PSCL_RANK3_BLK("%[kg]", "%[kb]", "[2,3,0,1]")
+                     PSCL_RANK3_BLK("%[kg]", "%[kb]", "[3,2,1,0]")
+                     PSCL_RANK3_BLK("%[mkg]", "%[mkb]", "[0,1,2,3]")
+                     PSCL_RANK3_BLK("%[mkg]", "%[mkb]", "[1,0,3,2]")
+                     PSCL_RANK3_BLK("%[mkg]", "%[mkb]", "[2,3,0,1]")
+                     PSCL_RANK3_BLK("%[mkg]", "%[mkb]", "[3,2,1,0]")
+                     : [t] "=&v"(t), [rg] "+v"(rg), [rbb] "+v"(rbb), [mkg] "=&v"(mkg), [mkb] "=&v"(mkb)
+                     : [kg] "v"(kg), [kb] "v"(kb)
+                     : "vcc");
+    }
+}
+#undef PSCL_RANK3_BLK
+
 // position of the j-th set bit (j < popcount(m)) of a mask of at most 32 bits, branch-free
 __device__ __forceinline__ uint32_t nth_set_bit16(uint32_t m, uint32_t j);
 __device__ __forceinline__ uint32_t nth_set_bit32(uint32_t m, uint32_t j) {
