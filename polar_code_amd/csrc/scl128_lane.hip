@@ -835,11 +835,14 @@ scl_lane_kernel(const pscl_decode_params P) {
                     const uint32_t kg = hiw(mg);
                     const uint32_t gmaxh = frame_max<G>(kg);
                     const bool ismax = kg == gmaxh;
-                    const uint32_t nmax = frame_sum<G>(ismax ? 1u : 0u);
-                    const uint32_t g2u = frame_max<G>(ismax ? 0u : kgu);
-                    const uint32_t wu = frame_max<G>(bad ? hiw_up(mb) : 0u);
+                    // (the certificate lane by lane -- a frame is deferred when ANY of its lanes sets
+                    // its bit of amb, so "every other better child" and "the near worse child" need no
+                    // frame reduction: each lane tests its own key, the ballot is the "for all")
+                    const uint32_t nmax = __builtin_popcount(frame_bits(wmask(ismax)));
+                    const bool g2ok = ismax || kgu < gmaxh;
+                    const bool wok = !bad || hiw_up(mb) < gmaxh;
                     const bool swap = bad8 != 0;
-                    amb |= wmask(swap && !(nmax == 1u && g2u < gmaxh && wu < gmaxh)) & vmask;
+                    amb |= wmask(swap && !(nmax == 1u && g2ok && wok)) & vmask;
                     src = lane_of(__builtin_ctz(bad8 | (1u << G)) & (G - 1));  // (frames without a swap: unused)
                     pull = swap && ismax;
                 } else
@@ -877,15 +880,16 @@ scl_lane_kernel(const pscl_decode_params P) {
                     const uint32_t kbu = hiw_up(mb);
                     const uint32_t su = keep_g ? (win_b ? kbu : kgu) : (win_b ? kbu : 0u);
                     const uint32_t nm = keep_g ? (win_b ? 0xffffffffu : kb) : kg;
-                    const uint32_t smax = frame_max<G>(su), nmin = frame_min<G>(nm);
+                    const uint32_t smax = frame_max<G>(su);
                     // exactly L survivors: the frame keeps L - d better children and popcount(w8)
                     // worse ones, so survivors == L iff popcount(w8) == d = popcount(f8) (the sum of
-                    // keep_g + win_b over the frame's lanes, which this replaces, is that count)
-                    amb |= wmask(!((uint32_t)__builtin_popcount(w8) == d && nmin > smax)) & vmask;
+                    // keep_g + win_b over the frame's lanes, which this replaces, is that count).
+                    // The margin lane by lane: every lane's non-survivor (0xffffffff: none) above the
+                    // frame's largest survivor -- the ballot into amb is the minimum over the frame
+                    amb |= wmask(!((uint32_t)__builtin_popcount(w8) == d && nm > smax)) & vmask;
                     // freed lanes take the surviving worse children: the j-th freed lane of a frame
-                    // pulls the j-th winner (both counted in lane order)
-                    const uint32_t j = __builtin_popcount(f8 & ((1u << p) - 1u));
-                    src = lane_of(nth_set_bit8(w8, j));
+                    // pulls the j-th winner (both counted in lane order; scl_lane.h)
+                    src = lane_of(matched_winner<G>(f8, w8, win_b, (uint32_t)p));
                     pull = !keep_g;
                 }
                 // the pull: bits, slot table and depth-5 / 6 registers of the source lane's path, in

@@ -137,6 +137,15 @@ __device__ __forceinline__ uint32_t frame_sum(uint32_t v) {
     if constexpr (G == 32) v += xrow32(v);
     return v;
 }
+template <int G>
+__device__ __forceinline__ uint32_t frame_or(uint32_t v) {
+    v |= dpp32<kQX1>(v);
+    v |= dpp32<kQX2>(v);
+    if constexpr (G >= 8) v |= dpp32<G >= 16 ? kHMIR : kFMIR>(v);
+    if constexpr (G >= 16) v |= dpp32<kRMIR>(v);
+    if constexpr (G == 32) v |= xrow32(v);
+    return v;
+}
 
 // Survivor selection of a full list (the L smallest of each frame's 2L children): this lane's
 // better child key kg and worse child key kb (kb >= kg: the worse child pays |llr| more).  Keys are
@@ -296,6 +305,26 @@ __device__ __forceinline__ uint32_t nth_set_bit8(uint32_t m, uint32_t j) {
     m = h2 ? (m >> 2) : m;
     const bool h1 = j >= (m & 1u);
     return (h4 ? 4u : 0u) + (h2 ? 2u : 0u) + (h1 ? 1u : 0u);
+}
+
+// The ranked tier's winner-to-freed-lane matching for frames of 4 or 8 lanes (the plain tier code of
+// scl128_lane.hip): the j-th freed lane of a frame pulls the j-th winner, both counted in lane order.
+// One packed word per frame, nibble k = the lane of the k-th winner: a winner of path index p ORs in
+// p << 4 r, r = its rank among the winners IN LANE ORDER (the set bits of w8 below p -- not its key
+// rank rbb: two winners of equal keys can both survive a passing certificate, and rbb would put both
+// in one nibble), over the frame's lanes (frame_or); the j-th freed lane reads nibble j.  Whatever the
+// two masks hold (a frame being deferred, a keeper's j past the winners) the lane read lies inside
+// the frame: the extract keeps log2 G bits.  (nth_set_bit8 above is the FS branch's form.)
+// w8 / win: the frame's winner mask and this lane's bit of it; f8: the frame's freed lanes; p: this
+// lane's path index; the result is the path index this lane pulls from if it is freed
+template <int G>
+__device__ __forceinline__ uint32_t matched_winner(uint32_t f8, uint32_t w8, bool win, uint32_t p) {
+    static_assert(G == 4 || G == 8, "the packed matching holds one nibble per lane of a frame of 4 or 8");
+    const uint32_t below = (1u << p) - 1u;
+    const uint32_t j = __builtin_popcount(f8 & below);
+    const uint32_t r = __builtin_popcount(w8 & below);
+    const uint32_t W = frame_or<G>(win ? p << (4u * r) : 0u);
+    return (W >> (4u * j)) & (uint32_t)(G - 1);
 }
 
 }  // namespace
