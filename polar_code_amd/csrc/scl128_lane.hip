@@ -153,6 +153,57 @@ __device__ __forceinline__ uint64_t flip_order_key(double q) {
 #ifndef PSCL_LANE_GSPLIT
 #define PSCL_LANE_GSPLIT 1
 #endif
+// PSPLAN (PSCL_LANE_PSPLAN, scl_lane.h): at the 56 even phases that are not recompute phases the first
+// rewritten depth's g nodes take their partial sums from a plan made at compile time -- the frozen
+// bits of the window dropped, one sign mask per distinct set of information bits -- instead of the
+// extract, transform and per-node shift of the runtime window; and the one-swap and ranked tiers'
+// certificates ballot each VALU compare and combine the masks in SALU.
+
+// The sign masks of a planned row of W g nodes on the window u[LO, LO + W) with the information bits
+// IW: psm[k] = node k's partial sum at bit 31 (S_k non-empty; the bits below are junk).  uw: the 32-bit
+// half of u0 / u1 that holds the window.  One shift per information bit, the sets' masks by psplan_mask.
+template <uint32_t IW, int W, int LO>
+__device__ __forceinline__ void psplan_row_masks(uint32_t uw, uint32_t (&psm)[8]) {
+    uint32_t mb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    static_for<W>([&](auto IC) {
+        constexpr int i = decltype(IC)::value;
+        if constexpr ((IW >> i) & 1u) mb[i] = uw << (31 - ((LO + i) & 31));
+    });
+    static_for<W>([&](auto KC) {
+        constexpr int k = decltype(KC)::value;
+        constexpr uint32_t S = psplan_set(IW, W, k);
+        psm[k] = 0;
+        if constexpr (S != 0) psm[k] = psplan_mask<S>(mb);
+    });
+}
+// g node K of a planned row: b + a (empty set), or the sign flip as one v_bitop3
+template <uint32_t IW, int W, int K>
+__device__ __forceinline__ double psplan_g_node(double a, double b, const uint32_t (&psm)[8]) {
+    if constexpr (psplan_set(IW, W, K) == 0) return b + a;
+    else return g_node_bit31(a, b, psm[K]);
+}
+// a planned row of two depth-6 g nodes from the path's depth-5 registers, and a planned row of W g
+// nodes of depth 4 or 5 from the parent slot's pairs in LDS (the kernel's own loops, with the plan's
+// nodes).  Written apart from the kernel body, which names no variable it did not name before and in
+// the same order: the FS, FP, EX and TXF instances then compile to the code they had, byte for byte
+// (tools/compare_kernels.py) -- a new local or lambda in the phase body moved their schedules.
+template <uint32_t IW, int LO>
+__device__ __forceinline__ void psplan_row_reg(uint32_t uw, const double (&r5)[4], double (&r6)[2]) {
+    uint32_t psm[8];
+    psplan_row_masks<IW, 2, LO>(uw, psm);
+    r6[0] = psplan_g_node<IW, 2, 0>(r5[0], r5[2], psm);
+    r6[1] = psplan_g_node<IW, 2, 1>(r5[1], r5[3], psm);
+}
+template <uint32_t IW, int W, int LO, int LMAX>
+__device__ __forceinline__ void psplan_row_lds(uint32_t uw, const double* in, double (&o)[W]) {
+    uint32_t psm[8];
+    psplan_row_masks<IW, W, LO>(uw, psm);
+    static_for<W>([&](auto KC) {
+        constexpr int k = decltype(KC)::value;
+        const double2 ab = *reinterpret_cast<const double2*>(in + k * LMAX * 2);
+        o[k] = psplan_g_node<IW, W, k>(ab.x, ab.y, psm);
+    });
+}
 
 // FS: the DL-SCL retry decodes (dlscl.hip, capi.cpp dl_retry_chunk) -- a round's entries read
 // bucket by bucket (P.elist), LLR rows by indirection (P.fidx), forced information bits (P.force:
@@ -272,6 +323,7 @@ scl_lane_kernel(const pscl_decode_params P) {
     constexpr bool BITS = !FS && !EX && PSCL_LANE_BITS;
     constexpr bool PLAIN = !FS && !EX && !TXF;  // the instances the PSCL_LANE_U0T / GSPLIT trims apply to
     constexpr bool U0T = PLAIN && PSCL_LANE_U0T;
+    constexpr bool PSPLAN = PLAIN && PSCL_LANE_PSPLAN;  // the partial-sum plan and the SALU-combined ballots
     constexpr bool GSPLIT = PLAIN && PSCL_LANE_GSPLIT && (LMAX == 8 || PSCL_LANE_CREG4);
     constexpr double MARGIN = BITS ? PSCL_TAIL2_MARGIN : PSCL_TAIL_ABS_MARGIN;
     auto hiw_up = [&](double m) {
@@ -531,11 +583,27 @@ scl_lane_kernel(const pscl_decode_params P) {
             }
             // ---- depths 4..6: this lane's own path; the first rewritten depth reads the parent slot
             if constexpr (start <= 6) {
-                uint32_t xsb = 0;  // partial sums of the first rewritten node's left sibling (g node)
+                // xsb: the partial sums of the first rewritten node's left sibling (g node k reads bit k).
+                // CAREFUL -- at a PLANNED phase (PSP below) it holds something else: the untransformed
+                // 32-bit half of u0 / u1 that contains the window, which only psplan_row_reg /
+                // psplan_row_lds read (the `(xsb >> k) & 1u` loops are not compiled there).  One variable
+                // for both, because a second local changed the code of the instances without the plan.
+                uint32_t xsb = 0;
+                // PSCL_LANE_PSPLAN (plain instances): the g nodes' partial sums from the compile-time
+                // plan (scl_lane.h) -- frozen window bits are 0, which the compiler cannot know once
+                // u0 / u1 have been through a pull (psplan_row_reg / psplan_row_lds above)
+                constexpr bool GW = phi && start >= 4 && start <= 6;  // a row of g nodes on a window of u
+                constexpr uint32_t iw = GW ? psplan_window(info0, info1, phi) : 0u;
+                constexpr bool PSP = GW && PSPLAN && psplan_planned(iw, GW ? psplan_width(phi) : 2);
                 if constexpr (phi && start >= 4) {
                     constexpr int w = 1 << (kn - start), lo = phi - w;
                     static_assert(phi <= 64 || lo >= 64, "u0 is not read bit-wise after phase 64 (PSCL_LANE_U0T)");
-                    xsb = polar_transform8((uint32_t)((lo >= 64 ? u1 : u0) >> (lo & 63)) & ((1u << w) - 1u));
+                    if constexpr (!PSP) {
+                        xsb = polar_transform8((uint32_t)((lo >= 64 ? u1 : u0) >> (lo & 63)) & ((1u << w) - 1u));
+                    } else {  // (a planned row: xsb = the 32-bit half of u that holds the window, untransformed)
+                        static_assert(w == psplan_width(phi) && psplan_proved(iw, w), "the partial-sum plan");
+                        xsb = (uint32_t)((lo >= 64 ? u1 : u0) >> (32 * ((lo & 63) >> 5)));
+                    }
                 }
                 static_for<3>([&](auto DI) {
                     constexpr int D = 4 + decltype(DI)::value;
@@ -548,18 +616,26 @@ scl_lane_kernel(const pscl_decode_params P) {
                         if constexpr (PSCL_LANE_REG56 && D == 6) {
                             // from this path's depth-5 registers (computed this phase, or carried
                             // along with the path since)
+                            if constexpr (!(PSP && is_g)) {
 #pragma unroll
-                            for (int k = 0; k < 2; ++k)
-                                r6[k] = is_g ? g_node(r5[k], r5[k + 2], (xsb >> k) & 1u) : f_minsum(r5[k], r5[k + 2]);
+                                for (int k = 0; k < 2; ++k)
+                                    r6[k] = is_g ? g_node(r5[k], r5[k + 2], (xsb >> k) & 1u) : f_minsum(r5[k], r5[k + 2]);
+                            } else {
+                                psplan_row_reg<iw, phi - 2>(xsb, r5, r6);
+                            }
                         } else {
                             const int sin = first ? slot_at(tab, D - 1) : p;  // (depth 3 at a recompute: own slot p)
                             const int sin_eff = (D == 4 && start <= 3) ? p : sin;
                             const double* in = Af + OFF_IN + sin_eff * 2;
                             double o[W];
+                            if constexpr (!(PSP && is_g)) {
 #pragma unroll
-                            for (int k = 0; k < W; ++k) {
-                                const double2 ab = *reinterpret_cast<const double2*>(in + k * LMAX * 2);
-                                o[k] = is_g ? g_node(ab.x, ab.y, (xsb >> k) & 1u) : f_minsum(ab.x, ab.y);
+                                for (int k = 0; k < W; ++k) {
+                                    const double2 ab = *reinterpret_cast<const double2*>(in + k * LMAX * 2);
+                                    o[k] = is_g ? g_node(ab.x, ab.y, (xsb >> k) & 1u) : f_minsum(ab.x, ab.y);
+                                }
+                            } else {
+                                psplan_row_lds<iw, W, phi - W, LMAX>(xsb, in, o);
                             }
                             if constexpr (PSCL_LANE_REG56 && D == 5) {
 #pragma unroll
@@ -842,7 +918,17 @@ scl_lane_kernel(const pscl_decode_params P) {
                     const bool g2ok = ismax || kgu < gmaxh;
                     const bool wok = !bad || hiw_up(mb) < gmaxh;
                     const bool swap = bad8 != 0;
-                    amb |= wmask(swap && !(nmax == 1u && g2ok && wok)) & vmask;
+                    if constexpr (!PSPLAN) {
+                        amb |= wmask(swap && !(nmax == 1u && g2ok && wok)) & vmask;
+                    } else {
+                        // (PSCL_LANE_PSPLAN: one ballot per VALU compare, the 64-bit masks combined in
+                        // SALU -- the ballot of a condition that was combined first is rebuilt from a
+                        // 0 / 1 select and a second compare.  Every lane is active here, so a mask's
+                        // complement is the negation)
+                        const uint64_t g2okm = wmask(ismax) | wmask(kgu < gmaxh);
+                        const uint64_t wokm = ~badm | wmask(hiw_up(mb) < gmaxh);
+                        amb |= wmask(swap) & ~(wmask(nmax == 1u) & g2okm & wokm) & vmask;
+                    }
                     src = lane_of(__builtin_ctz(bad8 | (1u << G)) & (G - 1));  // (frames without a swap: unused)
                     pull = swap && ismax;
                 } else
@@ -886,7 +972,10 @@ scl_lane_kernel(const pscl_decode_params P) {
                     // keep_g + win_b over the frame's lanes, which this replaces, is that count).
                     // The margin lane by lane: every lane's non-survivor (0xffffffff: none) above the
                     // frame's largest survivor -- the ballot into amb is the minimum over the frame
-                    amb |= wmask(!((uint32_t)__builtin_popcount(w8) == d && nm > smax)) & vmask;
+                    if constexpr (!PSPLAN)
+                        amb |= wmask(!((uint32_t)__builtin_popcount(w8) == d && nm > smax)) & vmask;
+                    else  // (the two compares' ballots combined in SALU, as in the one-swap tier)
+                        amb |= ~(wmask((uint32_t)__builtin_popcount(w8) == d) & wmask(nm > smax)) & vmask;
                     // freed lanes take the surviving worse children: the j-th freed lane of a frame
                     // pulls the j-th winner (both counted in lane order; scl_lane.h)
                     src = lane_of(matched_winner<G>(f8, w8, win_b, (uint32_t)p));

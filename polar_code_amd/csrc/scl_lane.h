@@ -18,7 +18,108 @@
 #define PSCL_LANE_BITS 1
 #endif
 
+// the partial sums of the first rewritten depth's g nodes at the even non-recompute phases resolved
+// at compile time from the information set (the plan below; scl128_lane.hip, plain instances)
+#ifndef PSCL_LANE_PSPLAN
+#define PSCL_LANE_PSPLAN 1
+#endif
+
 namespace {
+
+// ---- The partial-sum plan (plain constexpr: no device code, nothing of HIP).
+// At an even phase phi with t = phi mod 16 in {2, .., 14} the first rewritten depth is a row of w =
+// t & -t g nodes whose sign bits are the in-word Arikan transform of the window u[phi - w, phi): bit k
+// of polar_transform8(window) = the xor of the window bits i with (i & k) == k.  Frozen bits are 0,
+// so node k's partial sum is the parity of the window over S_k = {i : i an information bit, (i & k)
+// == k}, a set known at compile time: empty (the g node is b + a), the single bit decided at phi - 1,
+// or a handful of bits, the same set for several nodes.
+constexpr int psplan_width(int phi) { return (phi & 15) & -(phi & 15); }
+// the information bits of the window, bit i = position phi - w + i (a window never straddles a byte)
+constexpr uint32_t psplan_window(uint64_t info0, uint64_t info1, int phi) {
+    const int w = psplan_width(phi), lo = phi - w;
+    return (uint32_t)((lo >= 64 ? info1 : info0) >> (lo & 63)) & ((1u << w) - 1u);
+}
+// S_k as a mask of window positions
+constexpr uint32_t psplan_set(uint32_t iw, int w, int k) {
+    uint32_t s = 0;
+    for (int i = 0; i < w; ++i)
+        if (((iw >> i) & 1u) && (i & k) == k) s |= 1u << i;
+    return s;
+}
+// polar_transform8 (scl_device.h) restated as a constant expression: the same three stages
+constexpr uint32_t psplan_transform8(uint32_t x) {
+    x ^= (x >> 1) & 0x55u;
+    x ^= (x >> 2) & 0x33u;
+    x ^= (x >> 4) & 0x0fu;
+    return x;
+}
+// the proof: for every window value the frozen pattern allows (at most 2^8), the parity of window &
+// S_k is bit k of the transform -- a wrong plan fails the build (static_assert at every planned phase)
+constexpr bool psplan_proved(uint32_t iw, int w) {
+    for (uint32_t v = 0; v < (1u << w); ++v) {
+        if (v & ~iw) continue;
+        const uint32_t x = psplan_transform8(v);
+        for (int k = 0; k < w; ++k) {
+            uint32_t par = 0;
+            for (uint32_t m = v & psplan_set(iw, w, k); m; m &= m - 1u) par ^= 1u;
+            if (par != ((x >> k) & 1u)) return false;
+        }
+    }
+    return true;
+}
+// Instruction counts of the two forms of such a phase.  Transform form: extract (shift, and), two per
+// transform stage (shift, and-xor), two per node (shift to bit 31, xor).  Planned form, as emitted
+// (scl128_lane.hip): one shift per information bit of the window (its bit to bit 31), one xor per
+// distinct set of two or more bits that the masks are built through -- a set's mask is the mask of
+// the set without its lowest bit, xor that bit's, so sets that share their upper bits share the
+// work -- and one sign xor per node with a non-empty set.
+constexpr int psplan_cost_transform(int w) { return 2 + 2 * (w == 8 ? 3 : w == 4 ? 2 : 1) + 2 * w; }
+constexpr int psplan_cost(uint32_t iw, int w) {
+    uint32_t seen[64] = {};
+    int nseen = 0, cost = 0;
+    for (uint32_t m = iw; m; m &= m - 1u) ++cost;
+    for (int k = 0; k < w; ++k) {
+        uint32_t s = psplan_set(iw, w, k);
+        if (s) ++cost;
+        for (; s & (s - 1u); s &= s - 1u) {
+            bool dup = false;
+            for (int j = 0; j < nseen; ++j) dup = dup || seen[j] == s;
+            if (!dup) {
+                seen[nseen++] = s;
+                ++cost;
+            }
+        }
+    }
+    return cost;
+}
+// a phase keeps the transform where the plan is not cheaper (the densest windows of 8)
+constexpr bool psplan_planned(uint32_t iw, int w) { return psplan_cost(iw, w) < psplan_cost_transform(w); }
+// an information set's totals over the 56 phases: instructions per wavefront with the plan where it
+// is cheaper, and the number of phases that keep the transform
+constexpr int psplan_total(uint64_t info0, uint64_t info1) {
+    int tot = 0;
+    for (int phi = 2; phi < 128; phi += 2) {
+        if ((phi & 15) == 0) continue;
+        const int w = psplan_width(phi);
+        const uint32_t iw = psplan_window(info0, info1, phi);
+        tot += psplan_planned(iw, w) ? psplan_cost(iw, w) : psplan_cost_transform(w);
+    }
+    return tot;
+}
+constexpr int psplan_kept(uint64_t info0, uint64_t info1) {
+    int n = 0;
+    for (int phi = 2; phi < 128; phi += 2)
+        if ((phi & 15) != 0 && !psplan_planned(psplan_window(info0, info1, phi), psplan_width(phi))) ++n;
+    return n;
+}
+// the compiled-in sets (tests/test_lane_psplan_cpu.py restates the count in Python and reads these
+// figures from this file: the two cannot drift apart).  The transform form is 672 for any set.
+static_assert(psplan_total(0, 0) == 0 && psplan_kept(0, 0) == 0, "no information bit: every node is b + a");
+static_assert(psplan_total(kSpecInfo[1][0], kSpecInfo[1][1]) == 270 && psplan_kept(kSpecInfo[1][0], kSpecInfo[1][1]) == 0,
+              "partial-sum plan of the (128,64) set");
+static_assert(psplan_total(kSpecInfo[2][0], kSpecInfo[2][1]) == 378 && psplan_kept(kSpecInfo[2][0], kSpecInfo[2][1]) == 1 &&
+                  !psplan_planned(psplan_window(kSpecInfo[2][0], kSpecInfo[2][1], 120), 8),
+              "partial-sum plan of the (128,88) set: phase 120 keeps the transform");
 
 // intra-frame lane permutations of an 8-lane group (DPP controls): quad_perm xor 1, 2, 3, and the
 // half-row mirror (lane i <-> 7 - i), which maps one quad onto the other
@@ -325,6 +426,18 @@ __device__ __forceinline__ uint32_t matched_winner(uint32_t f8, uint32_t w8, boo
     const uint32_t r = __builtin_popcount(w8 & below);
     const uint32_t W = frame_or<G>(win ? p << (4u * r) : 0u);
     return (W >> (4u * j)) & (uint32_t)(G - 1);
+}
+
+// The partial-sum plan's sign mask of the set S (window positions, S != 0) from the per-bit masks
+// mb[i] (window bit i at bit 31): the mask of S without its lowest bit, xor that bit's.  Equal
+// sub-expressions of a phase's sets are one instruction (psplan_cost counts them so).
+template <uint32_t S>
+__device__ __forceinline__ uint32_t psplan_mask(const uint32_t (&mb)[8]) {
+    static_assert(S != 0 && S < 256u, "a non-empty set of window positions");
+    if constexpr ((S & (S - 1u)) == 0)
+        return mb[__builtin_ctz(S)];
+    else
+        return psplan_mask<(S & (S - 1u))>(mb) ^ mb[__builtin_ctz(S)];
 }
 
 }  // namespace
