@@ -169,6 +169,36 @@ int pscl_channel_device(pscl_handle* h, uint64_t seed, uint32_t stream_id, doubl
                         int k_payload, int64_t frame0, int64_t B, double* d_llr, uint64_t* d_msg);
 
 /*
+ * Caller payloads: the TX chain above on payloads the caller supplies instead of Philox draws.
+ *   d_payload [B][Wp] uint64, Wp = PSCL_WORDS(k_payload), k_payload = K - CRC degree (the payload is
+ *             the message when the handle has no CRC); bit j of a frame at word j / 64, bit j % 64.
+ *             Bits at and above k_payload are ignored.
+ * pscl_encode_device writes any subset of (a NULL pointer skips one; all NULL is PSCL_EINVAL):
+ *   d_msg   [B][W] uint64: attach_crc(payload), the layout of d_ref / d_best
+ *   d_code  [B][PSCL_WORDS(E)] uint64: the transmitted bits in transmission order, E = the
+ *           rate-matched length of pscl_set_rate_match or N without it; bit p is
+ *           x[order[p % N]] with rate matching (interleave, then truncate or repeat, scl_nr.py:23-35)
+ *           and x[p] without; bits past E in the last word are zero
+ *   d_sym   [B][E] BPSK symbols 1 - 2 x, float64 (sym_f32 = 0) or float32 (sym_f32 = 1)
+ * pscl_channel_payload_device adds pscl_channel_device's AWGN and writes
+ *   d_llr   [B][E] LLR rows, float64 (llr_f32 = 0) or float32 (llr_f32 = 1), or NULL
+ *   d_msg   as above, or NULL
+ * The noise is pscl_channel_device's stream -- key (seed, stream_id), counter (frame0 + frame,
+ * pair index) -- and the float64 expression is the same: called with the low k_payload bits of the
+ * message words pscl_channel_device writes, it reproduces that call's rows bit for bit.  A float32
+ * row is the float64 row rounded once, at the store.
+ * Both calls are enqueued on the handle's stream without a host wait; pending pipelined work is
+ * ordered first, as for pscl_channel_device.  B = 0 returns PSCL_OK without a launch.  PSCL_EINVAL
+ * for a NULL handle or payload, B < 0, frame0 < 0, every output NULL, rate <= 0 and a dtype flag
+ * outside {0, 1}; PSCL_EUNSUP for B above 4 * (2^31 - 1) frames, what one launch covers.
+ */
+int pscl_encode_device(pscl_handle* h, const uint64_t* d_payload, int64_t B, uint64_t* d_msg, uint64_t* d_code,
+                       void* d_sym, int sym_f32);
+int pscl_channel_payload_device(pscl_handle* h, const uint64_t* d_payload, uint64_t seed, uint32_t stream_id,
+                                double ebno_db, double rate, int64_t frame0, int64_t B, void* d_llr, int llr_f32,
+                                uint64_t* d_msg);
+
+/*
  * Uncoded BPSK baseline (run_fer_sweep.py:111-121, --include_uncoded) counted on the device:
  * per frame k_payload payload bits (the same Philox payload block as pscl_channel_device),
  * BPSK, AWGN with sigma^2 = 1 / (2 * 10^(ebno_db/10)) (rate 1), hard decision llr < 0.
@@ -662,6 +692,17 @@ int pscl_decode_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_p
 int pscl_decode_adaptive_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly, const double* llr,
                              int64_t B, int8_t* best_bits, uint8_t* crc_pass, int32_t* best_idx, uint8_t* stage,
                              int threads);
+
+/*
+ * pscl_encode_device's message and code words on the host, without a GPU or a handle: payload
+ * [B][PSCL_WORDS(K - CRC degree)] uint64 -> msg [B][W] (attach_crc, crc.py:19-37) and code
+ * [B][PSCL_WORDS(E or N)] (polar transform polar.py:17-29,106-119; E > 0: sub-block interleave and
+ * rate matching, scl_nr.py:23-35; E = 0: none).  Either output may be NULL, not both.  info_set
+ * and crc_poly as pscl_create.  PSCL_EINVAL for invalid arguments, PSCL_EUNSUP for E > N with
+ * N < 32 and for a CRC degree above PSCL_MAX_CRC.  No HIP call is made.
+ */
+int pscl_encode_cpu(int N, const int32_t* info_set, int K, uint64_t crc_poly, int E, const uint64_t* payload,
+                    int64_t B, uint64_t* msg, uint64_t* code);
 
 /* Launch geometry used by the decode kernel (for roofline bookkeeping): waves per
  * workgroup, workgroups per launch for B frames, LDS bytes per workgroup. */

@@ -49,6 +49,7 @@ EXPORTS = (
     "pscl_retry_device", "pscl_adaptive_dlscl_device", "pscl_simulate_adaptive_dl", "pscl_simulate_adaptive_dl_device",
     "pscl_f32_available", "pscl_decode_device_f32", "pscl_sc_device_f32", "pscl_escalate_device_f32",
     "pscl_adaptive_async_device_f32",
+    "pscl_encode_device", "pscl_channel_payload_device", "pscl_encode_cpu",
 )
 
 # pscl_set_tuning knobs (include/polar_scl.h)
@@ -128,6 +129,9 @@ def lib() -> C.CDLL:
         "pscl_sc_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp]),
         "pscl_escalate_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, P(_i64)]),
         "pscl_adaptive_async_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+        "pscl_encode_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, C.c_int]),
+        "pscl_channel_payload_device": (C.c_int, [_vp, _vp, _u64, C.c_uint32, _dbl, _dbl, _i64, _i64, _vp, C.c_int, _vp]),
+        "pscl_encode_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, _u64, C.c_int, _vp, _i64, _vp, _vp]),
         "pscl_simulate_adaptive_device": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, _vp]),
         "pscl_simulate_adaptive": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, _dbl, C.c_int, _i64, _i64, C.c_int, _vp]),
         "pscl_adaptive_stats": (C.c_int, [_vp, P(_i64), P(_i64), P(_i64), C.c_int]),
@@ -502,6 +506,33 @@ class Decoder:
                                         float(ebno_db), float(rate), int(k_payload), int(frame0), int(B), d_llr,
                                         d_msg or None))
 
+    # ---- caller payloads: d_payload points at [B][Wp] uint64, Wp = payload_words (include/polar_scl.h)
+    @property
+    def k_payload(self) -> int:
+        return self.K - self.crc_deg
+
+    @property
+    def payload_words(self) -> int:
+        return (self.k_payload + 63) // 64
+
+    @property
+    def code_words(self) -> int:
+        return ((self.E or self.N) + 63) // 64
+
+    def encode_device(self, d_payload: int, B: int, *, d_msg=0, d_code=0, d_sym=0, sym_f32: bool = False) -> None:
+        """payload -> message words, packed transmitted bits and BPSK symbols, any subset, enqueued
+        without a host wait (pscl_encode_device)."""
+        check(lib().pscl_encode_device(self._h, d_payload or None, int(B), d_msg or None, d_code or None, d_sym or None,
+                                       int(sym_f32)))
+
+    def channel_payload_device(self, d_payload: int, seed: int, stream_id: int, ebno_db: float, rate: float, frame0: int,
+                               B: int, *, d_llr=0, llr_f32: bool = False, d_msg=0) -> None:
+        """channel_device on the caller's payloads: the same noise stream, float64 or float32 rows
+        (pscl_channel_payload_device)."""
+        check(lib().pscl_channel_payload_device(self._h, d_payload or None, int(seed) & (2**64 - 1),
+                                                int(stream_id) & 0xFFFFFFFF, float(ebno_db), float(rate), int(frame0),
+                                                int(B), d_llr or None, int(llr_f32), d_msg or None))
+
     def path_llrs_device(self, d_llr: int, B: int, d_bits: int, d_out: int) -> None:
         """Decision LLRs [B, K] of the paths with information bits d_bits [B, W] (replay)."""
         with self._lock:
@@ -809,6 +840,26 @@ class CpuDecoder:
 
     def close(self) -> None:
         pass
+
+
+def encode_cpu(N: int, info_set, crc, payload_words: np.ndarray, E: int = 0):
+    """Decoder.encode_device's message and code words on the host (pscl_encode_cpu; no GPU):
+    payload_words [B, Wp] uint64 -> (msg [B, W] uint64, code [B, ceil((E or N) / 64)] uint64)."""
+    info = np.ascontiguousarray(np.asarray(info_set).astype(np.int32).ravel())
+    N, K, E, poly = int(N), int(info.size), int(E), poly_value(crc)
+    kp = K - max(poly.bit_length() - 1, 0)
+    pw = np.ascontiguousarray(payload_words, dtype=np.uint64)
+    if pw.ndim != 2 or pw.shape[1] != (max(kp, 0) + 63) // 64:
+        raise ValueError(f"payload_words must be [B, {(max(kp, 0) + 63) // 64}] uint64 words")
+    B = pw.shape[0]
+    msg = np.zeros((B, (K + 63) // 64 if K > 64 else 1), np.uint64)
+    code = np.zeros((B, (max(E or N, 1) + 63) // 64), np.uint64)
+    rc = lib().pscl_encode_cpu(N, info.ctypes.data_as(C.POINTER(_i32)), K, poly, E, _ptr(pw), B, _ptr(msg), _ptr(code))
+    if rc == PSCL_EINVAL:
+        raise ValueError("invalid code, CRC or rate-matched length for pscl_encode_cpu")
+    if rc == PSCL_EUNSUP:
+        raise NotImplementedError("repetition (E > N) needs N >= 32; CRC degree <= 32")
+    return msg, code
 
 
 _CACHE: dict = {}

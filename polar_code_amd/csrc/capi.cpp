@@ -2646,6 +2646,65 @@ int pscl_channel_device(pscl_handle* h, uint64_t seed, uint32_t stream_id, doubl
     return channel_launch(h, seed, stream_id, ebno_db, rate, k_payload, frame0, B, d_llr, d_msg, nullptr);
 }
 
+namespace {
+// the launch of the caller-payload TX (encode.hip): every argument is checked before any device call
+int encode_launch(pscl_handle* h, const uint64_t* d_payload, int64_t frame0, int64_t B, uint64_t* d_msg, uint64_t* d_code,
+                  void* d_rows, int row_mode, int row_f32, uint64_t seed, uint32_t stream_id, double ebno_db, double rate) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (!d_payload) return fail(PSCL_EINVAL, "d_payload is NULL");
+    if (B < 0 || frame0 < 0) return fail(PSCL_EINVAL, "B and frame0 must be >= 0");
+    if (!d_msg && !d_code && !d_rows) return fail(PSCL_EINVAL, "every output is NULL");
+    if (row_mode == PSCL_ROWS_LLR && !(rate > 0)) return fail(PSCL_EINVAL, "rate must be positive");
+    if (row_f32 != 0 && row_f32 != 1) return fail(PSCL_EINVAL, "the dtype flag must be 0 (float64) or 1 (float32)");
+    if (B > PSCL_ENCODE_MAX_B) return fail(PSCL_EUNSUP, "B exceeds the %lld frames of one launch", PSCL_ENCODE_MAX_B);
+    if (B == 0) return PSCL_OK;
+    const int rc = enter(h);
+    if (rc) return rc;
+    pscl_encode_params P;
+    memset(&P, 0, sizeof(P));
+    P.payload = d_payload;
+    P.B = B;
+    P.frame0 = frame0;
+    P.N = h->N;
+    P.K = h->K;
+    P.W = h->W;
+    P.k_payload = h->K - h->crc_deg;
+    P.Wp = PSCL_WORDS(P.k_payload);
+    P.crc_deg = h->crc_deg;
+    P.rm_E = h->rm_E;
+    P.row_mode = row_mode;
+    P.row_f32 = row_f32;
+    P.xtab = h->d_xtab;
+    P.crctab = h->d_crctab;
+    P.rm_order = h->d_rm_order;
+    P.msg = d_msg;
+    P.code = d_code;
+    P.rows = d_rows;
+    if (row_mode == PSCL_ROWS_LLR) {  // (channel_launch's parameters and channel_kernel's key)
+        const double nv = 1.0 / (2.0 * rate * pow(10.0, ebno_db / 10.0));
+        P.sigma = sqrt(nv);
+        P.llr_scale = 2.0 / nv;
+        P.k0 = (uint32_t)seed;
+        P.k1 = (uint32_t)(seed >> 32) ^ (stream_id * 0x85EBCA6Bu);
+    }
+    const hipError_t e = pscl_launch_encode(P, h->stream);
+    if (e != hipSuccess) return fail(PSCL_EDEVICE, "encode kernel launch: %s", hipGetErrorString(e));
+    return PSCL_OK;
+}
+}  // namespace
+
+int pscl_encode_device(pscl_handle* h, const uint64_t* d_payload, int64_t B, uint64_t* d_msg, uint64_t* d_code,
+                       void* d_sym, int sym_f32) {
+    return encode_launch(h, d_payload, 0, B, d_msg, d_code, d_sym, PSCL_ROWS_SYMBOLS, sym_f32, 0, 0, 0.0, 1.0);
+}
+
+int pscl_channel_payload_device(pscl_handle* h, const uint64_t* d_payload, uint64_t seed, uint32_t stream_id,
+                                double ebno_db, double rate, int64_t frame0, int64_t B, void* d_llr, int llr_f32,
+                                uint64_t* d_msg) {
+    return encode_launch(h, d_payload, frame0, B, d_msg, nullptr, d_llr, PSCL_ROWS_LLR, llr_f32, seed, stream_id, ebno_db,
+                         rate);
+}
+
 int pscl_set_rate_match(pscl_handle* h, int E) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     if (E < 0) return fail(PSCL_EINVAL, "E must be >= 0");

@@ -283,3 +283,57 @@ extern "C" int pscl_decode_cpu(int N, const int32_t* info_set, int K, int L, uin
     }
     return PSCL_OK;
 }
+
+// pscl_encode_device's message and code words on the host, as the plain bit loops of the reference:
+// attach_crc's long division (crc.py:19-37), u[info_set] = msg, the Arikan butterfly
+// (polar.py:17-29) and, for E > 0, bit p = x[order[p % N]] (interleaver.py:10-23 then
+// rate_match.py:8-16; the order is the identity for N < 32, as on the handle)
+extern "C" int pscl_encode_cpu(int N, const int32_t* info_set, int K, uint64_t crc_poly, int E, const uint64_t* payload,
+                               int64_t B, uint64_t* msg, uint64_t* code) {
+    if (N < 2 || N > PSCL_MAX_N || (N & (N - 1))) return PSCL_EINVAL;
+    if (K < 0 || K > N || B < 0 || E < 0 || !payload || (!msg && !code) || (K && !info_set)) return PSCL_EINVAL;
+    for (int i = 0; i < K; ++i)
+        if (info_set[i] < 0 || info_set[i] >= N || (i && info_set[i] <= info_set[i - 1])) return PSCL_EINVAL;
+    int deg = 0;
+    if (crc_poly) {
+        deg = 63 - __builtin_clzll(crc_poly);
+        if (deg <= 0 || K <= deg) return PSCL_EINVAL;  // crc.py:50-51 (message too short)
+        if (deg > PSCL_MAX_CRC) return PSCL_EUNSUP;
+    }
+    if (E > N && N < 32) return PSCL_EUNSUP;  // (pscl_set_rate_match)
+    const int kp = K - deg, Wp = PSCL_WORDS(kp), W = K > 64 ? PSCL_WORDS(K) : 1;
+    const int Et = E ? E : N, CW = PSCL_WORDS(Et), nb = (N + 31) / 32;
+    std::vector<uint8_t> bits((size_t)(K ? K : 1)), x((size_t)N);
+    for (int64_t b = 0; b < B; ++b) {
+        const uint64_t* pw = payload + b * Wp;
+        for (int j = 0; j < kp; ++j) bits[(size_t)j] = (uint8_t)((pw[j >> 6] >> (j & 63)) & 1);
+        for (int j = kp; j < K; ++j) bits[(size_t)j] = 0;
+        if (deg) {  // the remainder of payload * x^deg, left in the last deg positions
+            std::vector<uint8_t> buf(bits.begin(), bits.begin() + K);
+            for (int i = 0; i < kp; ++i) {
+                if (!buf[(size_t)i]) continue;
+                for (int k = 0; k <= deg; ++k) buf[(size_t)(i + k)] ^= (uint8_t)((crc_poly >> (deg - k)) & 1);
+            }
+            for (int j = kp; j < K; ++j) bits[(size_t)j] = buf[(size_t)j];
+        }
+        if (msg) {
+            uint64_t* mw = msg + b * W;
+            for (int w = 0; w < W; ++w) mw[w] = 0;
+            for (int j = 0; j < K; ++j) mw[j >> 6] |= (uint64_t)bits[(size_t)j] << (j & 63);
+        }
+        if (!code) continue;
+        std::fill(x.begin(), x.end(), (uint8_t)0);
+        for (int j = 0; j < K; ++j) x[(size_t)info_set[j]] = bits[(size_t)j];
+        for (int h = 1; h < N; h <<= 1)
+            for (int i = 0; i < N; i += 2 * h)
+                for (int j = i; j < i + h; ++j) x[(size_t)j] ^= x[(size_t)(j + h)];
+        uint64_t* cw = code + b * CW;
+        for (int c = 0; c < CW; ++c) cw[c] = 0;
+        for (int p = 0; p < Et; ++p) {
+            const int k = p % N;
+            const int pos = (E && N >= 32) ? (k % 32) * nb + k / 32 : k;
+            cw[p >> 6] |= (uint64_t)x[(size_t)pos] << (p & 63);
+        }
+    }
+    return PSCL_OK;
+}

@@ -258,6 +258,32 @@ struct pscl_channel_params {
     const int32_t* rm_order;     // [N] sub-block interleaver order
 };
 
+// Caller payloads (encode.hip; pscl_encode_device, pscl_channel_payload_device): channel_kernel's TX
+// chain with the payload loaded instead of drawn.  A block of its own -- a member more in
+// pscl_channel_params would move the argument offsets of every kernel that takes that block.
+// Outputs are chosen by non-null pointers.
+#define PSCL_ROWS_SYMBOLS 0  // rows = the BPSK symbols 1 - 2 x
+#define PSCL_ROWS_LLR 1      // rows = (symbol + sigma z) * llr_scale, z from channel_kernel's Philox stream
+struct pscl_encode_params {
+    const uint64_t* payload;     // [B][Wp]; bits at and above k_payload are ignored
+    int64_t B, frame0;
+    int N, K, W, Wp, k_payload, crc_deg;
+    int rm_E;                    // NR: E transmitted bits, bit p = x[rm_order[p % N]] (0: the N codeword bits)
+    int row_mode;                // PSCL_ROWS_*
+    int row_f32;                 // 1: rows are float32 (the float64 value rounded once at the store)
+    const uint64_t* xtab;        // [ceil(K/8)][256][2 or N/64] (pscl_channel_params)
+    const uint32_t* crctab;      // [ceil(k_payload/8)][256]
+    const int32_t* rm_order;     // [N]
+    uint64_t* msg;               // [B][W] or null: attach_crc(payload)
+    uint64_t* code;              // [B][ceil(E/64)] or null: the transmitted bits, packed
+    void* rows;                  // [B][E] double or float, or null
+    uint32_t k0, k1;             // Philox key of the noise (PSCL_ROWS_LLR)
+    double sigma, llr_scale;
+};
+// frames of one launch: its grid covers the batch in one pass (four frames per workgroup at N > 128)
+#define PSCL_ENCODE_MAX_B (4LL * 0x7fffffffLL)
+hipError_t pscl_launch_encode(const pscl_encode_params& P, hipStream_t s);
+
 // Lane-parallel successive cancellation of the N = 128 codes (sc128_lane.hip): stage 1 of
 // pscl_adaptive_device.  Frame b's hard-decision SC result (polar.py:130-168) goes to best / flags
 // (PSCL_FLAG_CRC_PASS | 0 when check_crc holds, else 0) and stage (1 pass, 2 fail).

@@ -74,13 +74,18 @@ class SCLDecoder:
     n_paths [B], and, when requested, metrics [B, L], cands [B, L, K], info_llrs [B, L, K].
     """
 
-    def __init__(self, N: int, info_set, L: int, crc_poly: Optional[str] = "0x1864CFB", device: int = 0):
+    def __init__(self, N: int, info_set, L: int, crc_poly: Optional[str] = "0x1864CFB", device=0):
         if L <= 0:
             raise ValueError("List size M must be positive")
-        self.N, self.L, self.crc_poly, self.device = int(N), int(L), crc_poly, int(device)
+        cpu = isinstance(device, str) and device == "cpu"
+        self.N, self.L, self.crc_poly, self.device = int(N), int(L), crc_poly, "cpu" if cpu else int(device)
         self.info_set = np.asarray(info_set).astype(np.int32)
         self.K = self.info_set.size
-        self._dec = _native.Decoder(self.N, self.info_set, self.L, crc_poly, self.device)
+        # device="cpu": the host decoder and encoder (pscl_decode_cpu, pscl_encode_cpu); no tensor methods
+        self._dec = (_native.CpuDecoder(self.N, self.info_set, self.L, crc_poly) if cpu
+                     else _native.Decoder(self.N, self.info_set, self.L, crc_poly, self.device))
+        self.k_payload = self.K - self._dec.crc_deg
+        self.payload_words = (self.k_payload + 63) // 64
 
     @property
     def native(self) -> _native.Decoder:
@@ -259,6 +264,114 @@ class SCLDecoder:
             llr.data_ptr(), B, **out, d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
             d_counters=counters.data_ptr() if counters is not None else 0)
         return best, flags, stage
+
+    # ---- caller payloads: payload -> CRC -> codeword (-> symbols or AWGN LLR rows) on the device
+    def encode(self, payload_bits: np.ndarray, device=None) -> dict:
+        """payload_bits [B, k_payload] 0/1 (k_payload = K - CRC degree) -> dict(msg [B, K] int8 =
+        attach_crc(payload), code [B, E] int8 = the transmitted bits: the codeword, or with rate
+        matching (native.set_rate_match) the interleaved, truncated or repeated codeword).  Host
+        arrays in and out; packs, calls pscl_encode_device and unpacks.  On a device="cpu" decoder,
+        or with device="cpu" here, the host form pscl_encode_cpu computes the same words."""
+        bits = np.asarray(payload_bits)
+        if bits.ndim == 1:
+            bits = bits[None, :]
+        if bits.ndim != 2 or bits.shape[1] != self.k_payload:
+            raise ValueError(f"payload_bits must be [B, {self.k_payload}]")
+        if np.any((bits != 0) & (bits != 1)):
+            raise ValueError("payload_bits entries must be 0 or 1")
+        B, E = bits.shape[0], self._dec.E or self.N
+        words = _pack_words(bits, self.payload_words)
+        if self.device == "cpu" or device == "cpu":
+            msg, code = _native.encode_cpu(self.N, self.info_set, self.crc_poly, words, self._dec.E)
+        else:
+            dec = self._dec
+            with _native.DeviceArena(dec) as mem:
+                d_pay = mem.alloc(max(words.nbytes, 8))
+                d_msg = mem.alloc(max(B * dec.W * 8, 8))
+                d_code = mem.alloc(max(B * dec.code_words * 8, 8))
+                if B:
+                    mem.upload(d_pay, words)
+                dec.encode_device(d_pay, B, d_msg=d_msg, d_code=d_code)
+                msg = mem.download(d_msg, max(B * dec.W * 8, 8), np.uint64)[:B * dec.W].reshape(B, dec.W)
+                code = mem.download(d_code, max(B * dec.code_words * 8, 8), np.uint64)[:B * dec.code_words]
+                code = code.reshape(B, dec.code_words)
+        return {"msg": _unpack_words(msg, self.K), "code": _unpack_words(code, E)}
+
+    def _payload_tensor(self, payload_words):
+        """Validate payload_words for the tensor methods -- a contiguous int64 [B, payload_words]
+        tensor on this decoder's GPU; anything else raises ValueError before any device call."""
+        import torch
+
+        if self.device == "cpu":
+            raise ValueError("the tensor methods need a GPU decoder (device='cpu' has encode())")
+        if (not isinstance(payload_words, torch.Tensor) or payload_words.dtype != torch.int64
+                or not payload_words.is_contiguous() or payload_words.dim() != 2
+                or payload_words.shape[1] != self.payload_words):
+            raise ValueError(f"payload_words must be a contiguous int64 [B, {self.payload_words}] tensor")
+        if payload_words.device.type != "cuda" or payload_words.device.index != self.device:
+            raise ValueError(f"payload_words must be on GPU {self.device}")
+        return payload_words.shape[0]
+
+    def encode_tensor(self, payload_words, symbols=None):
+        """Device path of encode on the caller's current torch stream, without a host wait:
+        payload_words [B, payload_words] int64 (the uint64 words' bits; bits from k_payload on are
+        ignored) -> (msg_words [B, W] int64, code_words [B, ceil(E / 64)] int64), and with symbols =
+        torch.float32 or torch.float64 also the BPSK symbols 1 - 2 code [B, E] of that dtype
+        (pscl_encode_device).  msg_words is what decode_tensor takes as ref_words."""
+        import torch
+
+        if symbols not in (None, torch.float32, torch.float64):
+            raise ValueError("symbols must be None, torch.float32 or torch.float64")
+        B = self._payload_tensor(payload_words)
+        dec, dev = self._dec, payload_words.device
+        msg = torch.empty((B, dec.W), dtype=torch.int64, device=dev)
+        code = torch.empty((B, dec.code_words), dtype=torch.int64, device=dev)
+        sym = None if symbols is None else torch.empty((B, dec.E or self.N), dtype=symbols, device=dev)
+        dec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        dec.encode_device(payload_words.data_ptr(), B, d_msg=msg.data_ptr(), d_code=code.data_ptr(),
+                          d_sym=0 if sym is None else sym.data_ptr(), sym_f32=symbols == torch.float32)
+        return (msg, code) if sym is None else (msg, code, sym)
+
+    def transmit_tensor(self, payload_words, ebno_db: float, *, seed: int, stream_id: int = 0, frame0: int = 0,
+                        rate: Optional[float] = None, dtype=None):
+        """encode_tensor's message sent over BPSK/AWGN at Eb/N0 = ebno_db (pscl_channel_payload_device):
+        returns (llr [B, E] of dtype torch.float64 (default) or torch.float32, msg_words [B, W] int64).
+        The noise of frame b is pscl_channel_device's for frame counter frame0 + b under (seed,
+        stream_id); rate defaults to k_payload / E (run_ber_sweep's convention).  float32 rows are
+        what decode_tensor decodes natively where native.f32_available()."""
+        import torch
+
+        dtype = torch.float64 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype must be torch.float32 or torch.float64")
+        if frame0 < 0:
+            raise ValueError("frame0 must be >= 0")
+        B = self._payload_tensor(payload_words)
+        dec, dev = self._dec, payload_words.device
+        E = dec.E or self.N
+        rate = self.k_payload / E if rate is None else float(rate)
+        if not rate > 0:
+            raise ValueError("rate must be positive")
+        llr = torch.empty((B, E), dtype=dtype, device=dev)
+        msg = torch.empty((B, dec.W), dtype=torch.int64, device=dev)
+        dec.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        dec.channel_payload_device(payload_words.data_ptr(), seed, stream_id, ebno_db, rate, frame0, B,
+                                   d_llr=llr.data_ptr(), llr_f32=dtype == torch.float32, d_msg=msg.data_ptr())
+        return llr, msg
+
+
+def _pack_words(bits: np.ndarray, words: int) -> np.ndarray:
+    """[B, n] 0/1 -> [B, words] uint64, bit j at word j // 64, bit j % 64."""
+    out = np.zeros((bits.shape[0], words * 8), np.uint8)
+    packed = np.packbits(bits.astype(np.uint8), axis=1, bitorder="little")
+    out[:, :packed.shape[1]] = packed
+    return out.view("<u8").astype(np.uint64).reshape(bits.shape[0], words)
+
+
+def _unpack_words(words: np.ndarray, n: int) -> np.ndarray:
+    """The inverse of _pack_words: the first n bits of each row as int8."""
+    by = np.ascontiguousarray(words.astype("<u8")).view(np.uint8).reshape(words.shape[0], -1)
+    return np.unpackbits(by, axis=1, bitorder="little")[:, :n].astype(np.int8)
 
 
 __all__ = ["decode_scl", "SCLDecoder"]
