@@ -12,22 +12,26 @@ POLY24 = "0x1864CFB"
 POLY16 = "0x11021"
 
 
-def make_llr(seed, B, info, crc, ebno_db, N=128, E=0, signal=True):
+def make_llr(seed, B, info, crc, ebno_db, N=128, E=0, signal=True, with_msg=False):
     """Host TX chain: payload, attach_crc, u[info] = msg, polar transform, BPSK, AWGN, LLR.
     One default_rng(seed) stream, frame by frame: the payload (integers' default dtype), then the
     frame's noise.  rate = K / N (kp / E rate matched, through subblock_interleave +
     rate_match_polar).  Returns
-    the rows handed to the decoder ([B, N] or [B, E]).  signal=False: noise-only rows."""
+    the rows handed to the decoder ([B, N] or [B, E]).  signal=False: noise-only rows.
+    crc=None: the payload is the message.  with_msg: (rows, msg [B, K] int8)."""
     rng = np.random.default_rng(seed)
     K = len(info)
-    deg = oracle.poly_int(crc).bit_length() - 1
+    deg = max(oracle.poly_int(crc).bit_length() - 1, 0)
     kp = K - deg
     n_out = E or N
     rate = kp / E if E else K / N
     nv = 1.0 / (2.0 * rate * 10 ** (ebno_db / 10))
     rows = np.empty((B, n_out))
+    msgs = np.empty((B, K), np.int8)
     for b in range(B):
-        msg = oracle.attach_crc(rng.integers(0, 2, size=kp).astype(np.int8), crc)
+        pay = rng.integers(0, 2, size=kp).astype(np.int8)
+        msg = oracle.attach_crc(pay, crc) if deg else pay
+        msgs[b] = msg
         u = np.zeros(N, np.int8)
         u[info] = msg
         x = oracle.polar_transform(u)
@@ -37,7 +41,7 @@ def make_llr(seed, B, info, crc, ebno_db, N=128, E=0, signal=True):
             x = rate_match_polar(subblock_interleave(x), E)
         sym = (1.0 - 2.0 * x) if signal else 0.0
         rows[b] = 2.0 * (sym + rng.normal(0.0, np.sqrt(nv), size=n_out)) / nv
-    return rows
+    return (rows, msgs) if with_msg else rows
 
 
 def internal_rows(rows, N, E):

@@ -24,6 +24,8 @@ Fixture sets:
   G15 decode_with_retries on quantised LLRs (exact |L0| / q ties in the flip ranking)  flip.py:104-108
   G16 decode_with_retries off the (128,64) code: N in {4..64}, K = N, (128,88), (128,100), short CRCs,
       retries >= K; beta random fp32 and None, tie-guarded (one shape: `make_golden.py g16`)         flip.py:65-141
+  G17 decode_scl on the (128,64) set under CRCs of degree 1 .. 32 and none, and on information sets
+      construct_info_set never gives (position 0, K = N, K < log2 M; `make_golden.py g17`)           scl.py:108-209
 """
 from __future__ import annotations
 
@@ -497,6 +499,52 @@ def g16():
     assert size < 1.5 * (OUT / "g7_flip.npz").stat().st_size, size
 
 
+def g17():
+    """decode_scl off the project's CRC and off constructed information sets: the (128,64) code under
+    polynomials of degree 1 .. 32 and none, and sets with position 0, without N - 1, K = N, and
+    fewer positions than log2 M (n_paths < M).  The cases and their rows are those of
+    tests/offcode_cases.py g17_cases() (a slice of what the off-code tests decode); the file holds
+    them (the rows by their hash) and the reference's outputs, one flat array per field
+    (offcode_cases.g17() unpacks)."""
+    for p in (OUT.parent, OUT.parent.parent, OUT.parent.parent / "oracle"):
+        if str(p) not in sys.path:
+            sys.path.insert(0, str(p))
+    from polar_code_amd import build
+
+    build.build_oracle()  # (the cases' rows come through the oracle's attach_crc / polar_transform)
+    import offcode_cases as oc
+
+    fields = {k: [] for k in ("info", "npaths", "best", "cands", "metrics", "info_llrs")}
+    tags, table, sha = [], [], []
+    seen = {"short_list": 0, "full_list": 0, "crc_fail": 0}
+    for tag, N, info, crc, M, rows in oc.g17_cases():
+        K = len(info)
+        tags.append(tag)
+        table.append([N, K, int(crc, 16) if crc else 0, M, len(rows)])
+        fields["info"].append(np.asarray(info, np.int16))
+        # (the Gaussian rows alone would be 41 KB of incompressible mantissas: the file holds each case's
+        # SHA-256 and offcode_cases.g17() repeats g17_cases()'s seeded draw, checked by the hash)
+        sha.append(oc.rows_sha(rows))
+        for llr in rows:
+            res = decode_scl(np.array(llr), np.array(info), M, crc=crc)
+            n, c, m, il, b = pack_decode(res, M, K)
+            assert 0 <= b < n
+            seen["short_list" if n < M else "full_list"] += 1
+            seen["crc_fail"] += bool(crc) and not check_crc(res["best_path_bits"], crc)
+            fields["npaths"].append(np.array([n], np.int32))
+            fields["best"].append(np.array([b], np.int32))
+            fields["cands"].append(c[:n].ravel())
+            fields["metrics"].append(m[:n])
+            fields["info_llrs"].append(il[:n].ravel())
+    assert all(v > 0 for v in seen.values()), seen
+    print("g17", len(tags), "cases", seen)
+    p = {"cases": np.array(tags), "table": np.array(table, np.int64), "llr_sha256": np.array(sha, "S")}
+    p.update({k: np.concatenate(v) for k, v in fields.items()})
+    save_stable(OUT / "g17_offcode.npz", p)
+    size = (OUT / "g17_offcode.npz").stat().st_size
+    assert size < (OUT / "g14_n256.npz").stat().st_size, size
+
+
 def main():
     if len(sys.argv) > 1:
         for name in sys.argv[1:]:
@@ -525,6 +573,7 @@ def main():
     g14()
     g15()
     g16()
+    g17()
     for p in sorted(OUT.glob("*.npz")):
         print(p.name, p.stat().st_size)
 

@@ -123,6 +123,30 @@ def test_decode_with_retries_short_and_odd_shapes():
                 np.testing.assert_array_equal(r["bits"], g[f"{tag}_{name}_bits"][f], err_msg=f"{tag} {name} {f}")
 
 
+def test_decode_scl_other_crcs_and_unconstructed_info_sets():
+    """g17: the (128,64) set under CRCs of degree 1, 6, 11, 16, 24, 32 and none at M = 8; the
+    information-set family of offcode_cases.py (position 0, without N - 1, K = N, 16-position blocks,
+    K = log2 M and K < log2 M) at N = 32, 128, M = 4, 8 and three of its sets at N = 256.  Path
+    count, every candidate, metric and decision LLR (as integer views) and the best index."""
+    import offcode_cases as oc
+
+    g = oc.g17()
+    assert [t for t, *_ in oc.g17_cases()] == list(g) and len(g) == 7 + 2 * 2 * 11 + 3
+    short = 0
+    for tag, c in g.items():
+        for f, llr in enumerate(c["llr"]):
+            n, cands, m, il, b = oracle.decode_scl(llr, c["info"], c["L"], crc=c["crc"])
+            assert n == c["npaths"][f], (tag, f)
+            assert n == oc.expected_paths(len(c["info"]), c["L"]), (tag, f)
+            short += n < c["L"]
+            np.testing.assert_array_equal(cands[:n], c["cands"][f], err_msg=f"{tag} frame {f}")
+            np.testing.assert_array_equal(m[:n].view(np.int64), c["metrics"][f].view(np.int64), err_msg=f"{tag} frame {f}")
+            np.testing.assert_array_equal(np.ascontiguousarray(il[:n]).view(np.int64), c["info_llrs"][f].view(np.int64),
+                                          err_msg=f"{tag} frame {f}")
+            assert b == c["best"][f], (tag, f)
+    assert short >= 20  # (first_only, last_only, short and fills_last below its list size)
+
+
 def test_batch_matches_single(golden):
     g = golden("g4_decode.npz")
     llr = g["M8_snr3_llr"]
