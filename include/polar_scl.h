@@ -450,6 +450,49 @@ int pscl_adaptive_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, i
                                int32_t* d_n_escalated);
 
 /*
+ * DL-SCL on float32 rows: the float32 contract above, carried on to the retry chains.  d_llr is
+ * [B][N] (or [B][E]) float32, 4-byte aligned; the other arguments are those of the float64 forms.
+ * Every output and every counter -- d_best, d_flags, d_stage, d_attempts, d_tried, d_n_escalated, each
+ * counter block, d_out -- equals the float64 form's on the rows widened value by value, on a pipelined
+ * handle too: a value is widened where a kernel loads it (rate-matched values first, then combined in
+ * float64), and flip metric, tie rule (lower index), beta, warm start, stop rule and tried_stride are
+ * the float64 forms'.  The row type belongs to the call: it is kept with the call's arguments, so the
+ * chains a pipelined call leaves to the next call (or pscl_join) read the rows as their own call gave
+ * them, and float64 and float32 calls may alternate on one handle.
+ *
+ * pscl_dlscl_device_f32, pscl_retry_device_f32 and pscl_adaptive_dlscl_device_f32 are native exactly
+ * where pscl_f32_available(h) is 1.  The baseline is the float32 plain decode: pscl_decode_device_f32's
+ * launches (at L = 4 too, where PSCL_TUNE_DL_LANE would move the float64 baseline to a kernel without a
+ * float32 form; the results are the same by construction), pscl_adaptive_async_device_f32's
+ * stream-ordered launches for the three-stage call, the caller's for pscl_retry_device_f32.  The retry
+ * rounds are the default chain's instances over float rows: the screened lane-per-path retry decode
+ * with its exact side chain ((128,64), plain rows), exact forced-bit rounds ((128,88), rate-matched
+ * rows), and the post pass in its wide and narrow forms at 2 and 4 entries per wavefront.
+ * PSCL_TUNE_DL_CHUNKS, PSCL_TUNE_DL_SPLIT, PSCL_TUNE_DL_SCREEN (and _MIN), PSCL_TUNE_DL_WARM_APX and
+ * PSCL_TUNE_POST_EPW select among those and stay native.  Two knobs select an instance that was not
+ * built over float rows and are refused: with PSCL_TUNE_DL_FUSED_POST = 1 or PSCL_TUNE_DL_RETRY_LANE = 2
+ * on a (128,64) handle the three calls return PSCL_EUNSUP with a message that names the knob (nothing
+ * else runs in its place, so pscl_path_stats stays truthful).  Elsewhere they return PSCL_EUNSUP with
+ * pscl_decode_device_f32's message.  The float64 forms' argument errors come first, with the same
+ * codes; PSCL_EINVAL without a CRC (pscl_dlscl_device_f32 too: a chain needs one).
+ *
+ * pscl_path_llrs_device_f32 is the decision-LLR replay from float32 rows; d_out stays float64 and
+ * equals pscl_path_llrs_device's on the widened rows bit for bit.  It takes every N = 128 handle (any
+ * information set, plain and rate-matched rows), as pscl_sc_device_f32; PSCL_EUNSUP for other N.
+ */
+int pscl_dlscl_device_f32(pscl_handle* h, const float* d_llr, int64_t B, int retries, uint64_t* d_best,
+                          uint8_t* d_flags, int32_t* d_attempts, int32_t* d_tried, int tried_stride,
+                          const uint64_t* d_ref, int k_payload, int64_t* d_counters_scl, int64_t* d_counters_dl);
+int pscl_retry_device_f32(pscl_handle* h, const float* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
+                          uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried, int tried_stride,
+                          const uint64_t* d_ref, int k_payload, int64_t* d_counters_dl);
+int pscl_adaptive_dlscl_device_f32(pscl_handle* h, const float* d_llr, int64_t B, int retries, uint64_t* d_best,
+                                   uint8_t* d_flags, uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried,
+                                   int tried_stride, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                                   int32_t* d_n_escalated);
+int pscl_path_llrs_device_f32(pscl_handle* h, const float* d_llr, int64_t B, const uint64_t* d_bits, double* d_out);
+
+/*
  * One SNR point of a Monte-Carlo sweep with the three-stage decoder, for global frames
  * [frame0, frame0 + B): the TX (and the optional uncoded baseline) with the Philox stream of
  * pscl_simulate and pscl_simulate_adaptive -- shards add up exactly -- then

@@ -49,6 +49,7 @@ EXPORTS = (
     "pscl_retry_device", "pscl_adaptive_dlscl_device", "pscl_simulate_adaptive_dl", "pscl_simulate_adaptive_dl_device",
     "pscl_f32_available", "pscl_decode_device_f32", "pscl_sc_device_f32", "pscl_escalate_device_f32",
     "pscl_adaptive_async_device_f32",
+    "pscl_dlscl_device_f32", "pscl_retry_device_f32", "pscl_adaptive_dlscl_device_f32", "pscl_path_llrs_device_f32",
     "pscl_encode_device", "pscl_channel_payload_device", "pscl_encode_cpu",
 )
 
@@ -129,6 +130,13 @@ def lib() -> C.CDLL:
         "pscl_sc_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp]),
         "pscl_escalate_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, P(_i64)]),
         "pscl_adaptive_async_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+        "pscl_dlscl_device_f32": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp,
+                                            _vp]),
+        "pscl_retry_device_f32": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int,
+                                            _vp]),
+        "pscl_adaptive_dlscl_device_f32": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                                                     C.c_int, _vp, _vp]),
+        "pscl_path_llrs_device_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
         "pscl_encode_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, C.c_int]),
         "pscl_channel_payload_device": (C.c_int, [_vp, _vp, _u64, C.c_uint32, _dbl, _dbl, _i64, _i64, _vp, C.c_int, _vp]),
         "pscl_encode_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, _u64, C.c_int, _vp, _i64, _vp, _vp]),
@@ -538,6 +546,12 @@ class Decoder:
         with self._lock:
             check(lib().pscl_path_llrs_device(self._h, d_llr, int(B), d_bits, d_out))
 
+    def path_llrs_device_f32(self, d_llr: int, B: int, d_bits: int, d_out: int) -> None:
+        """path_llrs_device on float32 rows (pscl_path_llrs_device_f32; N = 128, any information set);
+        d_out stays float64."""
+        with self._lock:
+            check(lib().pscl_path_llrs_device_f32(self._h, d_llr, int(B), d_bits, d_out))
+
     def path_llrs(self, llr: np.ndarray, bits: np.ndarray) -> np.ndarray:
         """Host form of path_llrs_device: llr [B, N] (or [B, E]), bits [B, K] 0/1."""
         llr = np.ascontiguousarray(llr, dtype=np.float64)
@@ -606,6 +620,38 @@ class Decoder:
                                                    d_flags or None, d_stage or None, d_attempts or None, d_tried or None,
                                                    int(tried_stride), d_ref or None, int(k_payload), d_counters or None,
                                                    d_n_escalated or None))
+
+    def dlscl_device_f32(self, d_llr: int, B: int, retries: int, *, beta=None, d_best: int, d_flags: int,
+                         d_attempts=0, d_tried=0, tried_stride=0, d_ref=0, k_payload=0, d_counters_scl=0,
+                         d_counters_dl=0) -> None:
+        """dlscl_device on float32 rows (pscl_dlscl_device_f32): native where f32_available(), else it
+        raises (PSCL_EUNSUP)."""
+        self.set_beta(beta)
+        with self._lock:
+            check(lib().pscl_dlscl_device_f32(self._h, d_llr or None, int(B), int(retries), d_best or None,
+                                              d_flags or None, d_attempts or None, d_tried or None, int(tried_stride),
+                                              d_ref or None, int(k_payload), d_counters_scl or None,
+                                              d_counters_dl or None))
+
+    def retry_device_f32(self, d_llr: int, B: int, retries: int, *, beta=None, d_best: int, d_flags: int, d_stage=0,
+                         d_attempts=0, d_tried=0, tried_stride=0, d_ref=0, k_payload=0, d_counters_dl=0) -> None:
+        """retry_device on float32 rows (pscl_retry_device_f32)."""
+        self.set_beta(beta)
+        with self._lock:
+            check(lib().pscl_retry_device_f32(self._h, d_llr or None, int(B), int(retries), d_best or None,
+                                              d_flags or None, d_stage or None, d_attempts or None, d_tried or None,
+                                              int(tried_stride), d_ref or None, int(k_payload), d_counters_dl or None))
+
+    def adaptive_dlscl_device_f32(self, d_llr: int, B: int, retries: int, *, beta=None, d_best: int, d_flags: int,
+                                  d_stage=0, d_attempts=0, d_tried=0, tried_stride=0, d_ref=0, k_payload=0,
+                                  d_counters=0, d_n_escalated=0) -> None:
+        """adaptive_dlscl_device on float32 rows (pscl_adaptive_dlscl_device_f32)."""
+        self.set_beta(beta)
+        with self._lock:
+            check(lib().pscl_adaptive_dlscl_device_f32(self._h, d_llr or None, int(B), int(retries), d_best or None,
+                                                       d_flags or None, d_stage or None, d_attempts or None,
+                                                       d_tried or None, int(tried_stride), d_ref or None,
+                                                       int(k_payload), d_counters or None, d_n_escalated or None))
 
     def uncoded_device(self, seed: int, stream_id: int, ebno_db: float, k_payload: int, frame0: int, B: int,
                        d_counters: int) -> None:

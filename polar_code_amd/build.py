@@ -24,16 +24,18 @@ ARCH = os.environ.get("PSCL_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 HIP_SOURCES = ["scl_kernels.hip", "scl128.hip", "scl128_spec.hip", "scl128_lane.hip", "scl128_lane_rl.hip", "sc128_lane.hip",
-               "scl128_lane_f32.hip", "scl128_lane_rl_f32.hip", "sc128_lane_f32.hip", "scl128_spec_f32.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "encode.hip", "capi.cpp",
+               "scl128_lane_f32.hip", "scl128_lane_rl_f32.hip", "scl128_lane_fs_f32.hip", "sc128_lane_f32.hip", "scl128_spec_f32.hip", "scl128_spec_fs_f32.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "dlscl_f32.hip", "encode.hip", "capi.cpp",
                "scl_cpu.cpp"]
 HIP_DEPS = HIP_SOURCES + ["scl_kernels.h", "scl_device.h", "scl128_impl.h", "scl_lane.h", "glibc_softplus.h", "exp_table.inc"]
 # scl128_spec.hip is compiled once per (information-set code, list size): 8 objects
 SPEC_UNITS = [(c, l) for c in (1, 2) for l in (1, 2, 4, 8)]
-# scl128_spec_f32.hip (the exact re-decode over float32 rows) likewise: 4 objects
+# scl128_spec_f32.hip (the exact re-decode over float32 rows) and scl128_spec_fs_f32.hip (the exact
+# forced-bit retry decode over float32 rows) likewise: 4 objects each
 SPEC_F32_UNITS = [(c, l) for c in (1, 2) for l in (4, 8)]
 # units that compile another unit's source with a switch (the source is part of their content key)
 WRAPPED = {"scl128_lane_rl.hip": "scl128_lane.hip", "scl128_lane_f32.hip": "scl128_lane.hip",
-           "scl128_lane_rl_f32.hip": "scl128_lane.hip", "sc128_lane_f32.hip": "sc128_lane.hip"}
+           "scl128_lane_rl_f32.hip": "scl128_lane.hip", "scl128_lane_fs_f32.hip": "scl128_lane.hip",
+           "sc128_lane_f32.hip": "sc128_lane.hip", "dlscl_f32.hip": "dlscl.hip"}
 
 
 BASE_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result", "-Wno-unused-value"]
@@ -70,10 +72,10 @@ def hip_units(objdir: Path, tag: str = "", hash_: str | None = None) -> list[tup
             for c, l in SPEC_UNITS:
                 units.append((CSRC / src, [f"-DPSCL_SPEC_CODE={c}", f"-DPSCL_SPEC_LMAX={l}"],
                               objdir / f"scl128_spec_{c}_{l}{tag}.o"))
-        elif src == "scl128_spec_f32.hip":
+        elif src in ("scl128_spec_f32.hip", "scl128_spec_fs_f32.hip"):
             for c, l in SPEC_F32_UNITS:
                 units.append((CSRC / src, [f"-DPSCL_SPEC_CODE={c}", f"-DPSCL_SPEC_LMAX={l}"],
-                              objdir / f"scl128_spec_f32_{c}_{l}{tag}.o"))
+                              objdir / f"{Path(src).stem}_{c}_{l}{tag}.o"))
         else:
             extra = [f'-DPSCL_BUILD_HASH="{hash_}"'] if (src == "capi.cpp" and hash_) else []
             units.append((CSRC / src, extra, objdir / (Path(src).stem + tag + ".o")))

@@ -103,6 +103,8 @@ struct pscl_dl_call {
     bool pipe = false;
     int mode = 0;                 // the baseline (DlBase): 0 the list decode, 1 adaptive, 2 the caller's
     uint8_t* d_stage = nullptr;   // (modes 1, 2) 3 at every frame that enters a chain
+    bool row_f32 = false;         // d_llr points at float32 rows (the pscl_*_f32 forms): the type of this
+                                  // call's rows, kept with its arguments for the chains enqueued later
 };
 
 // depth of the DL-SCL pipeline (pscl_set_pipelined): a pipelined call's compaction output and, for
@@ -1344,12 +1346,16 @@ int pscl_set_tuning(pscl_handle* h, int knob, int64_t value) {
     return PSCL_OK;
 }
 
-int pscl_path_llrs_device(pscl_handle* h, const double* d_llr, int64_t B, const uint64_t* d_bits, double* d_out) {
+namespace {
+// pscl_path_llrs_device and (f32: d_llr points at float32 rows) pscl_path_llrs_device_f32
+int path_llrs_impl(pscl_handle* h, const void* d_llr, bool f32, int64_t B, const uint64_t* d_bits, double* d_out) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
     if (B == 0) return PSCL_OK;
     if (!d_llr || !d_bits || !d_out) return fail(PSCL_EINVAL, "d_llr, d_bits and d_out are required");
     if (h->N > PSCL_FAST_N) return fail(PSCL_EUNSUP, "decision-LLR replay supports N <= %d", PSCL_FAST_N);
+    if (f32 && h->N != PSCL_FAST_N)
+        return fail(PSCL_EUNSUP, "float32 rows: the decision-LLR replay takes N = %d only (N = %d)", PSCL_FAST_N, h->N);
     if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
     int rc = enter(h);
     if (rc) return rc;
@@ -1362,7 +1368,8 @@ int pscl_path_llrs_device(pscl_handle* h, const double* d_llr, int64_t B, const 
     if (e != hipSuccess) return fail(PSCL_EDEVICE, "iota launch: %s", hipGetErrorString(e));
     pscl_replay_params Rp;
     memset(&Rp, 0, sizeof(Rp));
-    Rp.llr = d_llr;
+    Rp.llr = (const double*)d_llr;  // (f32: floats; the float32 instance takes the launch)
+    Rp.row_f32 = f32 ? 1 : 0;
     Rp.N = h->N;
     Rp.n = h->n;
     Rp.K = h->K;
@@ -1380,6 +1387,15 @@ int pscl_path_llrs_device(pscl_handle* h, const double* d_llr, int64_t B, const 
         return fail(PSCL_EDEVICE, "replay launch: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(h->stream));  // d_cnt is a host-staged value
     return PSCL_OK;
+}
+}  // namespace
+
+int pscl_path_llrs_device(pscl_handle* h, const double* d_llr, int64_t B, const uint64_t* d_bits, double* d_out) {
+    return path_llrs_impl(h, d_llr, false, B, d_bits, d_out);
+}
+
+int pscl_path_llrs_device_f32(pscl_handle* h, const float* d_llr, int64_t B, const uint64_t* d_bits, double* d_out) {
+    return path_llrs_impl(h, d_llr, true, B, d_bits, d_out);
 }
 
 int pscl_set_beta(pscl_handle* h, const double* beta) {
@@ -1454,6 +1470,26 @@ struct DlState {
 #define PSCL_DL_WARM_APX_DEFAULT 1  // (measured: profiles/r06t_warm_apx_ab.txt)
 #endif
 
+// float32 rows in a DL-SCL call (pscl_dlscl_device_f32, pscl_retry_device_f32,
+// pscl_adaptive_dlscl_device_f32): why this handle's chains have no float32 kernels, or null where they
+// have -- the handles of f32_unsupported, whose default chains are native (the screened lane-per-path
+// retry decode with the exact side chain for the (128,64) code, exact retry rounds for the rate-matched
+// (128,88) code, the post pass in its wide and narrow forms at 2 and 4 entries per wavefront; chunks,
+// splits, PSCL_TUNE_DL_SCREEN and PSCL_TUNE_DL_WARM_APX select among those).  Two knobs select an
+// instance that was not built over float rows and are refused by name rather than run as something
+// else, which pscl_path_stats would misreport.
+const char* f32_chain_unsupported(const pscl_handle* h) {
+    if (const char* why = f32_unsupported(h)) return why;
+    if (!h->rm_E) {  // (the rate-matched chains screen nothing: the two knobs do not apply)
+        const int64_t fk = h->tune[PSCL_TUNE_DL_FUSED_POST];
+        if (fk == 1 || (fk == 0 && PSCL_DL_FUSED_POST_DEFAULT))
+            return "PSCL_TUNE_DL_FUSED_POST selects the retry decode with the fused post pass, which has no float32 form";
+        if (h->tune[PSCL_TUNE_DL_RETRY_LANE] == 2)
+            return "PSCL_TUNE_DL_RETRY_LANE = 2 selects the two-lanes-per-path screened retry decode, which has no float32 form";
+    }
+    return nullptr;
+}
+
 hipError_t launch_post(pscl_handle* h, const pscl_post_params& Q, int64_t A, hipStream_t s) {
     if (pscl_post_epw(Q) == 4) h->n_post_epw4++;
     return pscl_launch_dl_post(Q, A, s);
@@ -1461,7 +1497,9 @@ hipError_t launch_post(pscl_handle* h, const pscl_post_params& Q, int64_t A, hip
 
 int dl_retry_chunk(pscl_handle* h, const DlState& S, int A, int rounds, const double* d_llr, uint64_t* d_best,
                    uint8_t* d_flags, int32_t* d_attempts, int32_t* d_tried, int tried_stride, int64_t* d_cnt_dl,
-                   hipStream_t st, hipStream_t side, hipEvent_t ev_s, hipEvent_t ev_d, bool narrow, bool beside) {
+                   hipStream_t st, hipStream_t side, hipEvent_t ev_s, hipEvent_t ev_d, bool narrow, bool beside, bool f32) {
+    // f32: d_llr points at float32 rows (a handle with float32 chains, f32_chain_unsupported; the
+    // callers check) -- every post pass and every retry decode below is the float32 instance
     const int K = h->K, W = h->W;
     hipError_t e;
     const size_t bstride = (size_t)PSCL_DL_NSEG * PSCL_DL_CSTRIDE;
@@ -1469,6 +1507,7 @@ int dl_retry_chunk(pscl_handle* h, const DlState& S, int A, int rounds, const do
     pscl_post_params Q;
     memset(&Q, 0, sizeof(Q));
     Q.llr = d_llr;
+    Q.row_f32 = f32 ? 1 : 0;  // (QD and the launches' copies inherit it)
     Q.N = h->N;
     Q.n = h->n;
     Q.K = K;
@@ -1507,6 +1546,7 @@ int dl_retry_chunk(pscl_handle* h, const DlState& S, int A, int rounds, const do
     pscl_decode_params H;
     fill_decode_params(h, H, 0);
     H.llr = d_llr;
+    pscl_set_row_type(H, f32);  // (HA and HX inherit it)
     H.B = A;
     H.fidx = S.act;
     H.force = S.force;
@@ -1879,7 +1919,7 @@ int dl_chain(pscl_handle* h, const pscl_dl_call& a, const DlBufs& b, int64_t c, 
         int r2 = dl_retry_chunk(h, T, k ? A - A0 : A0, a.rounds, a.d_llr, a.d_best, a.d_flags, a.d_attempts,
                                 a.d_tried, a.tried_stride, d_cdl, h->retry_stream[cs + k],
                                 (h->tune[PSCL_TUNE_DL_STREAMS] & 1) ? h->retry_stream[cs + k] : h->side_stream[cs + k],
-                                h->ev_scr[cs + k], h->ev_def[cs + k], a.pipe, beside);
+                                h->ev_scr[cs + k], h->ev_def[cs + k], a.pipe, beside, a.row_f32);
         if (r2) return r2;
     }
     if (parts == 2) {  // both chains done before the parity's indices are reused
@@ -1936,6 +1976,9 @@ struct DlBase {
     uint8_t* d_stage = nullptr;
     int64_t* d_counters_sc = nullptr;
     int32_t* d_n_escalated = nullptr;
+    // d_llr points at float32 rows: the baseline is the float32 plain decode (pscl_decode_device_f32's
+    // launches in mode 0, pscl_adaptive_async_device_f32's in mode 1) and the chains the float32 ones
+    bool row_f32 = false;
 };
 int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
                int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref, int k_payload,
@@ -1953,13 +1996,29 @@ int pscl_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, int retrie
                       d_counters_scl, d_counters_dl, nullptr);
 }
 
+int pscl_dlscl_device_f32(pscl_handle* h, const float* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
+                          int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref, int k_payload,
+                          int64_t* d_counters_scl, int64_t* d_counters_dl) {
+    DlBase base;
+    base.row_f32 = true;
+    return dlscl_impl(h, (const double*)d_llr, B, retries, d_best, d_flags, d_attempts, d_tried, tried_stride, d_ref,
+                      k_payload, d_counters_scl, d_counters_dl, nullptr, base);
+}
+
 // Retry rounds on the caller's baseline (include/polar_scl.h): dlscl_impl with the baseline skipped.
-int pscl_retry_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
-                      uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref,
-                      int k_payload, int64_t* d_counters_dl) {
+namespace {
+int retry_args(pscl_handle* h, const uint64_t* d_ref, const int64_t* d_counters_dl) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     if (!h->crc_poly) return fail(PSCL_EINVAL, "retry rounds need a CRC (without one every baseline passes)");
     if (d_ref && !d_counters_dl) return fail(PSCL_EINVAL, "d_ref given without d_counters_dl");
+    return PSCL_OK;
+}
+}  // namespace
+
+int pscl_retry_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
+                      uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref,
+                      int k_payload, int64_t* d_counters_dl) {
+    if (const int rc = retry_args(h, d_ref, d_counters_dl)) return rc;
     DlBase base;
     base.mode = 2;
     base.d_stage = d_stage;
@@ -1967,19 +2026,43 @@ int pscl_retry_device(pscl_handle* h, const double* d_llr, int64_t B, int retrie
                       d_counters_dl, nullptr, base);
 }
 
+int pscl_retry_device_f32(pscl_handle* h, const float* d_llr, int64_t B, int retries, uint64_t* d_best, uint8_t* d_flags,
+                          uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried, int tried_stride, const uint64_t* d_ref,
+                          int k_payload, int64_t* d_counters_dl) {
+    if (const int rc = retry_args(h, d_ref, d_counters_dl)) return rc;
+    DlBase base;
+    base.mode = 2;
+    base.d_stage = d_stage;
+    base.row_f32 = true;
+    return dlscl_impl(h, (const double*)d_llr, B, retries, d_best, d_flags, d_attempts, d_tried, tried_stride, d_ref, k_payload,
+                      nullptr, d_counters_dl, nullptr, base);
+}
+
 // The three-stage decode (include/polar_scl.h): dlscl_impl on the adaptive baseline.
-int pscl_adaptive_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best,
-                               uint8_t* d_flags, uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried,
-                               int tried_stride, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
-                               int32_t* d_n_escalated) {
+namespace {
+// the checks before dlscl_impl's own; done: B = 0, nothing is left to enqueue
+int adaptive_dlscl_args(pscl_handle* h, int64_t B, const uint64_t* d_ref, int k_payload, const int64_t* d_counters,
+                        int32_t* d_n_escalated, bool* done) {
+    *done = false;
     int rc = adaptive_async_args(h, B, k_payload);
     if (rc) return rc;
     if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
     if (B == 0) {
+        *done = true;
         if ((rc = enter(h))) return rc;
         if (d_n_escalated) HIP_TRY(hipMemsetAsync(d_n_escalated, 0, 4, h->stream));
-        return PSCL_OK;
     }
+    return PSCL_OK;
+}
+}  // namespace
+
+int pscl_adaptive_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint64_t* d_best,
+                               uint8_t* d_flags, uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried,
+                               int tried_stride, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                               int32_t* d_n_escalated) {
+    bool done;
+    const int rc = adaptive_dlscl_args(h, B, d_ref, k_payload, d_counters, d_n_escalated, &done);
+    if (rc || done) return rc;
     DlBase base;
     base.mode = 1;
     base.d_stage = d_stage;
@@ -1988,6 +2071,24 @@ int pscl_adaptive_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, i
     return dlscl_impl(h, d_llr, B, retries, d_best, d_flags, d_attempts, d_tried, tried_stride, d_ref, k_payload,
                       d_counters ? d_counters + PSCL_NCOUNT : nullptr, d_counters ? d_counters + 2 * PSCL_NCOUNT : nullptr,
                       nullptr, base);
+}
+
+int pscl_adaptive_dlscl_device_f32(pscl_handle* h, const float* d_llr, int64_t B, int retries, uint64_t* d_best,
+                                   uint8_t* d_flags, uint8_t* d_stage, int32_t* d_attempts, int32_t* d_tried,
+                                   int tried_stride, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
+                                   int32_t* d_n_escalated) {
+    bool done;
+    const int rc = adaptive_dlscl_args(h, B, d_ref, k_payload, d_counters, d_n_escalated, &done);
+    if (rc || done) return rc;
+    DlBase base;
+    base.mode = 1;
+    base.d_stage = d_stage;
+    base.d_counters_sc = d_counters;
+    base.d_n_escalated = d_n_escalated;
+    base.row_f32 = true;
+    return dlscl_impl(h, (const double*)d_llr, B, retries, d_best, d_flags, d_attempts, d_tried, tried_stride, d_ref,
+                      k_payload, d_counters ? d_counters + PSCL_NCOUNT : nullptr,
+                      d_counters ? d_counters + 2 * PSCL_NCOUNT : nullptr, nullptr, base);
 }
 
 namespace {
@@ -2004,6 +2105,11 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
     const int rounds = h->crc_poly && retries > 0 ? (retries < h->K ? retries : h->K) : 0;
     if (d_tried && tried_stride < rounds) return fail(PSCL_EINVAL, "tried_stride < min(retries, K)");
     if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
+    const bool f32 = base.row_f32;
+    if (f32) {
+        if (!h->crc_poly) return fail(PSCL_EINVAL, "float32 DL-SCL chains need a CRC (without one every baseline passes)");
+        if (const char* why = f32_chain_unsupported(h)) return fail(PSCL_EUNSUP, "%s", why);
+    }
     struct HostClock {  // pscl_host_stats: this call's wall time on the host
         pscl_handle* h;
         std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -2027,6 +2133,7 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
     a.k_payload = k_payload;
     a.d_counters_dl = d_counters_dl;
     a.mode = mode;
+    a.row_f32 = f32;
     a.d_stage = mode ? base.d_stage : nullptr;
     // Chunks (tuning knob PSCL_TUNE_DL_CHUNKS, default 1): the baseline decodes run in order on the handle's
     // stream; the retry entries of chunk c are split over two chains, each on its own retry
@@ -2091,7 +2198,8 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
         // baseline SCL (flip.py:79-80) of chunk c
         pscl_decode_params P;
         fill_decode_params(h, P, 0);
-        P.llr = d_llr + c0 * row;
+        P.llr = f32 ? (const double*)((const float*)d_llr + c0 * row) : d_llr + c0 * row;
+        pscl_set_row_type(P, f32);
         P.B = nc;
         P.best = d_best + c0 * W;
         P.flags = d_flags + c0;
@@ -2104,7 +2212,9 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
         if (rounds > 0) {
             const int64_t dl_lane = h->tune[PSCL_TUNE_DL_LANE] ? h->tune[PSCL_TUNE_DL_LANE]
                                                                : (PSCL_DL_LANE_DEFAULT ? PSCL_DL_LANE_DEFAULT : (h->L == 8 ? 1 : 2));
-            P.no_lane = dl_lane != 1;
+            // (float32 rows: the lane-per-path kernel at both L -- the two-lanes-per-path screening
+            // kernel has no float32 form, and the results are the same by construction)
+            P.no_lane = dl_lane != 1 && !f32;
         }
         if (tx) {  // the fused TX: the lane kernel draws the chunk's rows (simulate_enqueue checked it applies)
             P.no_lane = 0;
@@ -2141,7 +2251,7 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
         if (mode == 1) {
             int q = 0;
             if ((rc = adaptive_begin(h, false, &q))) return rc;
-            if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, base.d_stage))) return rc;
+            if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, base.d_stage, f32))) return rc;
             if (d_ref && (e = pscl_launch_dl_count(d_best, d_flags, d_ref, B, W, k_payload, base.d_counters_sc, s)) != hipSuccess)
                 return fail(PSCL_EDEVICE, "dl_count launch: %s", hipGetErrorString(e));
             hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -2159,7 +2269,7 @@ int dlscl_impl(pscl_handle* h, const double* d_llr, int64_t B, int retries, uint
                 HIP_TRY(hipEventRecord(t0, s));
             }
             if ((rc = adaptive_escalate_enqueue(h, q, false, d_llr, B, d_best, d_flags, d_ref, k_payload, d_counters_scl,
-                                                base.d_n_escalated)))
+                                                base.d_n_escalated, f32)))
                 return rc;
             if (t1) HIP_TRY(hipEventRecord(t1, s));
         } else if (mode == 0) {

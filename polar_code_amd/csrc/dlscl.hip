@@ -39,6 +39,20 @@
 
 #pragma clang fp contract(off)
 
+// Float32 rows (the pscl_*_f32 DL-SCL calls and pscl_path_llrs_device_f32): dlscl_f32.hip compiles this
+// file with PSCL_DLSCL_F32_UNIT and gets the post pass and the replay over float rows under names of
+// their own (dl_post_kernel_r32<..>, replay_kernel_r32: r32 for float32 rows), and their launches -- nothing else.  The one
+// difference is the load site (load_row / load_rowq and nr_stage's float overload): a value is widened
+// as it is loaded, exactly, and the rest is this file's fp64 code.  The float64 code object holds
+// exactly what it held before.
+#ifdef PSCL_DLSCL_F32_UNIT
+using post_llr_t = float;
+#define dl_post_kernel dl_post_kernel_r32
+#define replay_kernel replay_kernel_r32
+#else
+using post_llr_t = double;
+#endif
+
 namespace {
 
 using pscl::f_minsum;
@@ -77,6 +91,7 @@ __device__ __forceinline__ uint64_t order_key(double q) {
     return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
 }
 
+#ifndef PSCL_DLSCL_F32_UNIT
 using pscl::wave_sum;
 
 // failing baseline frames of a chunk -> act[] (entry e holds frame base + f); list[e] = e.
@@ -113,15 +128,16 @@ __global__ void __launch_bounds__(256) iota64_kernel(int64_t* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = i;
 }
+#endif  // PSCL_DLSCL_F32_UNIT
 
 // Channel LLRs p = lane and lane + 64 of a frame row (rate matched: de-rate-matched and
 // de-interleaved on the fly); N <= 128
-__device__ __forceinline__ void load_row(const double* llr_row, int rm_E, const int32_t* rm_src, int N, double& c0,
+__device__ __forceinline__ void load_row(const post_llr_t* llr_row, int rm_E, const int32_t* rm_src, int N, double& c0,
                                          double& c1) {
     const int lane = threadIdx.x & 63;
     c0 = c1 = 0.0;
-    if (lane < N) c0 = rm_E == 0 ? llr_row[lane] : pscl::nr_stage(llr_row, rm_src[lane], rm_E, N);
-    if (lane + 64 < N) c1 = rm_E == 0 ? llr_row[lane + 64] : pscl::nr_stage(llr_row, rm_src[lane + 64], rm_E, N);
+    if (lane < N) c0 = rm_E == 0 ? (double)llr_row[lane] : pscl::nr_stage(llr_row, rm_src[lane], rm_E, N);
+    if (lane + 64 < N) c1 = rm_E == 0 ? (double)llr_row[lane + 64] : pscl::nr_stage(llr_row, rm_src[lane + 64], rm_E, N);
 }
 
 // Leaf LLRs of a path with information bits (b0, b1), top-down through the tree (one
@@ -203,7 +219,7 @@ __global__ void __launch_bounds__(256) replay_kernel(const pscl_replay_params R,
     uint64_t u[2];
     int jpos[2];
     double c0, c1;
-    load_row(R.llr + row * (R.rm_E ? R.rm_E : R.N), R.rm_E, R.rm_src, R.N, c0, c1);
+    load_row(reinterpret_cast<const post_llr_t*>(R.llr) + row * (R.rm_E ? R.rm_E : R.N), R.rm_E, R.rm_src, R.N, c0, c1);
     const double* cur = replay_leaves(c0, c1, R.N, R.n, R.info_mask, bw[0], R.W > 1 ? bw[1] : 0ULL, lvl[wave][0],
                                       lvl[wave][1], u, jpos);
     double* out = R.out + (int64_t)e * R.K;
@@ -309,11 +325,11 @@ struct PostShared {
 
 // Channel LLRs p = hl + HLN m (m < 128 / HLN) of a frame row, N <= 128 (HLN lanes per entry)
 template <int HLN>
-__device__ __forceinline__ void load_rowq(const double* row, int rm_E, const int32_t* rm_src, int N, int hl, double* c) {
+__device__ __forceinline__ void load_rowq(const post_llr_t* row, int rm_E, const int32_t* rm_src, int N, int hl, double* c) {
 #pragma unroll
     for (int m = 0; m < PSCL_FAST_N / HLN; ++m) {
         const int p = hl + HLN * m;
-        c[m] = p < N ? (rm_E == 0 ? row[p] : pscl::nr_stage(row, rm_src[p], rm_E, N)) : 0.0;
+        c[m] = p < N ? (rm_E == 0 ? (double)row[p] : pscl::nr_stage(row, rm_src[p], rm_E, N)) : 0.0;
     }
 }
 
@@ -455,7 +471,8 @@ __global__ void __launch_bounds__(PW * 64) __attribute__((amdgpu_waves_per_eu(EP
         double c[EL];
         auto bc32 = [&](uint32_t v, int base) { return slot_bcast32<EPW>(v, base, hs); };
         auto bc64 = [&](uint64_t v, int base) { return slot_bcast64<EPW>(v, base, hs); };
-        load_rowq<HLN>(Q.llr + (int64_t)bc64((uint64_t)mf, 0) * (Q.rm_E ? Q.rm_E : N), Q.rm_E, Q.rm_src, N, hl, c);
+        const post_llr_t* const rows = reinterpret_cast<const post_llr_t*>(Q.llr);
+        load_rowq<HLN>(rows + (int64_t)bc64((uint64_t)mf, 0) * (Q.rm_E ? Q.rm_E : N), Q.rm_E, Q.rm_src, N, hl, c);
         for (int it = 0; it < npair; ++it) {
             const int sb = EPW * it, src = sb + hs;  // this entry slot's metadata lane
             bool valid = src < nval;
@@ -465,7 +482,7 @@ __global__ void __launch_bounds__(PW * 64) __attribute__((amdgpu_waves_per_eu(EP
             const int nt = Q.init ? 0 : (int)bc32((uint32_t)mnt, sb);
             auto prefetch = [&]() {  // (metadata lanes past nval hold entry 0's: a valid row)
                 if (it + 1 < npair)
-                    load_rowq<HLN>(Q.llr + (int64_t)bc64((uint64_t)mf, sb + EPW) * (Q.rm_E ? Q.rm_E : N),
+                    load_rowq<HLN>(rows + (int64_t)bc64((uint64_t)mf, sb + EPW) * (Q.rm_E ? Q.rm_E : N),
                                    Q.rm_E, Q.rm_src, N, hl, c);
             };
             bool more;
@@ -910,6 +927,7 @@ __global__ void __launch_bounds__(PW * 64) __attribute__((amdgpu_waves_per_eu(EP
         atomicAdd(reinterpret_cast<unsigned long long*>(Q.counters) + PSCL_CNT_RETRIES, decodes);
 }
 
+#ifndef PSCL_DLSCL_F32_UNIT
 // Post pass of the long codes (N > PSCL_FAST_N): one wavefront per entry, no replay -- the
 // retry decodes run the HIST kernel, so the attempt's best-path decision LLRs (L0, scl.py:158,
 // 166) arrive with it.  Per entry: final-attempt bookkeeping and the CRC stop rule
@@ -1042,8 +1060,18 @@ __global__ void __launch_bounds__(256) dl_mark_stage_kernel(const int64_t* __res
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         stage[act[i]] = (uint8_t)value;
 }
+#endif  // PSCL_DLSCL_F32_UNIT
 
 }  // namespace
+
+// (PSCL_DLSCL_F32_UNIT: the launches of the two kernels over float32 rows; a launch whose rows are of
+// the other type is refused)
+#ifdef PSCL_DLSCL_F32_UNIT
+#define PSCL_REPLAY_LAUNCH pscl_launch_replay_f32
+#define PSCL_POST_LAUNCH pscl_launch_dl_post_f32
+#else
+#define PSCL_REPLAY_LAUNCH pscl_launch_replay
+#define PSCL_POST_LAUNCH pscl_launch_dl_post
 
 hipError_t pscl_launch_dl_mark_stage(const int64_t* act, int64_t n, uint8_t* stage, int value, hipStream_t s) {
     if (n <= 0) return hipSuccess;
@@ -1072,14 +1100,20 @@ hipError_t pscl_launch_iota64(int64_t* out, int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(iota64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, n);
     return hipGetLastError();
 }
+#endif  // PSCL_DLSCL_F32_UNIT
 
-hipError_t pscl_launch_replay(const pscl_replay_params& R, int64_t cap, hipStream_t s) {
+hipError_t PSCL_REPLAY_LAUNCH(const pscl_replay_params& R, int64_t cap, hipStream_t s) {
+#ifndef PSCL_DLSCL_F32_UNIT
+    if (R.row_f32) return pscl_launch_replay_f32(R, cap, s);  // (dlscl_f32.hip)
+#endif
+    if ((R.row_f32 != 0) != (sizeof(post_llr_t) == 4)) return hipErrorInvalidValue;
     if (cap <= 0) return hipSuccess;
     const int64_t grid = (cap + 3) / 4;
     hipLaunchKernelGGL(replay_kernel, dim3((unsigned)grid), dim3(256), 0, s, R, cap);
     return hipGetLastError();
 }
 
+#ifndef PSCL_DLSCL_F32_UNIT
 // entries per wavefront of the launch (the 4-entry form is instantiated for the (128,64) code: its
 // K = 64 sums fit 3 wavefronts per SIMD without spills; others run 2 entries per wavefront)
 int pscl_post_epw(const pscl_post_params& Q) {
@@ -1087,8 +1121,13 @@ int pscl_post_epw(const pscl_post_params& Q) {
     if (!(Q.N == 128 && Q.K == 64)) return 2;
     return Q.epw == 2 || Q.epw == 4 ? Q.epw : kPostEpwNarrow;
 }
+#endif  // PSCL_DLSCL_F32_UNIT
 
-hipError_t pscl_launch_dl_post(const pscl_post_params& Q, int64_t entries, hipStream_t s) {
+hipError_t PSCL_POST_LAUNCH(const pscl_post_params& Q, int64_t entries, hipStream_t s) {
+#ifndef PSCL_DLSCL_F32_UNIT
+    if (Q.row_f32) return pscl_launch_dl_post_f32(Q, entries, s);  // (dlscl_f32.hip)
+#endif
+    if ((Q.row_f32 != 0) != (sizeof(post_llr_t) == 4)) return hipErrorInvalidValue;
     if (entries <= 0) return hipSuccess;
     // workgroups of PW wavefronts (EPW PW entries in flight), sized for `pairs` iterations per wavefront
     const int PW = Q.narrow ? kPostWavesNarrow : kPostWavesWide;
@@ -1124,6 +1163,7 @@ hipError_t pscl_launch_dl_post(const pscl_post_params& Q, int64_t entries, hipSt
     return hipGetLastError();
 }
 
+#ifndef PSCL_DLSCL_F32_UNIT
 hipError_t pscl_launch_dl_count(const uint64_t* best, const uint8_t* flags, const uint64_t* ref, int64_t B, int W,
                                 int k_payload, int64_t* counters, hipStream_t s) {
     int64_t grid = (B + 1023) / 1024;  // (four frames per thread)
@@ -1133,3 +1173,4 @@ hipError_t pscl_launch_dl_count(const uint64_t* best, const uint8_t* flags, cons
                        counters);
     return hipGetLastError();
 }
+#endif  // PSCL_DLSCL_F32_UNIT

@@ -20,6 +20,13 @@ PSCL_SPEC_F32_DECL(1, 4)
 PSCL_SPEC_F32_DECL(1, 8)
 PSCL_SPEC_F32_DECL(2, 4)
 PSCL_SPEC_F32_DECL(2, 8)
+// the exact forced-bit decodes of a DL-SCL retry round over float32 rows (scl128_spec_fs_f32.hip)
+#define PSCL_SPEC_FS_F32_DECL(c, l) \
+    hipError_t pscl_launch_spec_fs_f32_##c##_##l(const pscl_decode_params& P, int wpg, int64_t grid, int lds, hipStream_t s);
+PSCL_SPEC_FS_F32_DECL(1, 4)
+PSCL_SPEC_FS_F32_DECL(1, 8)
+PSCL_SPEC_FS_F32_DECL(2, 4)
+PSCL_SPEC_FS_F32_DECL(2, 8)
 
 namespace {
 
@@ -42,15 +49,20 @@ int spec_code(const pscl_decode_params& P) {
 template <int LMAX>
 hipError_t launch128(const pscl_decode_params& P, int hist, int wpg, int64_t grid, int lds, hipStream_t s) {
     const bool fs = P.force || P.sc_hard;
-    if (P.f32) {  // float32 rows: the exact plain decode of a compiled-in code at L = 4, 8, nothing else
-        if (hist || fs || P.apx || P.L != LMAX || P.metrics || P.cands) return hipErrorInvalidValue;
+    if (P.f32) {  // float32 rows: the exact decode of a compiled-in code at L = 4, 8 (plain, or the
+                  // forced-bit decode of a DL-SCL retry round), nothing else
+        if (hist || P.sc_hard || P.apx || P.L != LMAX || P.metrics || P.cands) return hipErrorInvalidValue;
         const int code = spec_code(P);
         if constexpr (LMAX == 4) {
-            if (code == 1 && !P.rm_E) return pscl_launch_spec_f32_1_4(P, wpg, grid, lds, s);
-            if (code == 2 && P.rm_E) return pscl_launch_spec_f32_2_4(P, wpg, grid, lds, s);
+            if (code == 1 && !P.rm_E)
+                return fs ? pscl_launch_spec_fs_f32_1_4(P, wpg, grid, lds, s) : pscl_launch_spec_f32_1_4(P, wpg, grid, lds, s);
+            if (code == 2 && P.rm_E)
+                return fs ? pscl_launch_spec_fs_f32_2_4(P, wpg, grid, lds, s) : pscl_launch_spec_f32_2_4(P, wpg, grid, lds, s);
         } else if constexpr (LMAX == 8) {
-            if (code == 1 && !P.rm_E) return pscl_launch_spec_f32_1_8(P, wpg, grid, lds, s);
-            if (code == 2 && P.rm_E) return pscl_launch_spec_f32_2_8(P, wpg, grid, lds, s);
+            if (code == 1 && !P.rm_E)
+                return fs ? pscl_launch_spec_fs_f32_1_8(P, wpg, grid, lds, s) : pscl_launch_spec_f32_1_8(P, wpg, grid, lds, s);
+            if (code == 2 && P.rm_E)
+                return fs ? pscl_launch_spec_fs_f32_2_8(P, wpg, grid, lds, s) : pscl_launch_spec_f32_2_8(P, wpg, grid, lds, s);
         }
         return hipErrorInvalidValue;
     }

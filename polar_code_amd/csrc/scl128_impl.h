@@ -63,9 +63,15 @@ constexpr int kn = 7;
 // defines PSCL_SCL128_F32 before it includes this file and gets scl128_kernel over float rows under a
 // name of its own (scl128_kernel_f32<..>): a channel value is widened where it is loaded (the in-place
 // reads of the plain form, the LDS staging store of the CH form); the rest is the fp64 code.
+// scl128_spec_fs_f32.hip defines PSCL_SCL128_F32_FS too: the forced-bit instances of a DL-SCL retry
+// round over float rows, named scl128_fs_kernel_r32<..>.
 #ifdef PSCL_SCL128_F32
 using llr128_t = float;
+#ifdef PSCL_SCL128_F32_FS
+#define scl128_kernel scl128_fs_kernel_r32
+#else
 #define scl128_kernel scl128_kernel_f32
+#endif
 #else
 using llr128_t = double;
 #endif

@@ -55,9 +55,16 @@
 // (scl_lane_kernel_f32<..>), and their launches.  The one difference is the load site (chan / chan_at
 // and nr_stage's float overload): a value is widened as it is loaded, exactly, and the rest is this
 // file's fp64 code.  The float64 code objects hold exactly what they held before.
+// scl128_lane_fs_f32.hip adds PSCL_LANE_FS_UNIT and gets the forced-bit instances of a screened DL-SCL
+// retry round over float rows (rows by indirection through the entry lists), named
+// scl_lane_fs_kernel_r32<..>, and their launch.
 #ifdef PSCL_LANE_F32_UNIT
 using lane_llr_t = float;
+#ifdef PSCL_LANE_FS_UNIT
+#define scl_lane_kernel scl_lane_fs_kernel_r32  // (r32: float32 rows)
+#else
 #define scl_lane_kernel scl_lane_kernel_f32
+#endif
 #else
 using lane_llr_t = double;
 #endif
@@ -1459,6 +1466,24 @@ hipError_t PSCL_LANE_RL_LAUNCH(const pscl_decode_params& P, int64_t grid, hipStr
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
+#elif defined(PSCL_LANE_FS_UNIT)
+// the forced-bit screening instances over float32 rows (scl128_lane_fs_f32.hip: the screened retry
+// rounds of the pscl_*_f32 DL-SCL calls); pscl_launch_lane_fs's launches without the fused post pass,
+// whose replay reads the row as doubles
+#ifndef PSCL_LANE_F32_UNIT
+#error "PSCL_LANE_FS_UNIT builds the float32 forced-bit instances: define PSCL_LANE_F32_UNIT too"
+#endif
+hipError_t pscl_launch_lane_fs_f32(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
+    const int lds8 = LaneLayout<8>::F * LaneLayout<8>::FSTRIDE * 8, lds4 = LaneLayout<4>::F * LaneLayout<4>::FSTRIDE * 8;
+    if (!P.f32 || P.fpost) return hipErrorInvalidValue;
+    if (P.L == 8)
+        hipLaunchKernelGGL((scl_lane_kernel<8, 1, true>), dim3((unsigned)grid), dim3(64), lds8, s, P);
+    else if (P.L == 4)
+        hipLaunchKernelGGL((scl_lane_kernel<4, 1, true>), dim3((unsigned)grid), dim3(64), lds4, s, P);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
 #elif defined(PSCL_LANE_F32_UNIT)
 // the plain instances over float32 rows (pscl_launch_lane's launches; no fused TX form)
 hipError_t pscl_launch_lane_f32(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
@@ -1553,8 +1578,8 @@ hipError_t pscl_launch_lane_exact(const pscl_decode_params& P, hipStream_t s) {
 hipError_t pscl_launch_lane_fs(const pscl_decode_params& P, int64_t grid, hipStream_t s) {
     const int lds8 = LaneLayout<8>::F * (P.fpost ? LaneLayout<8>::FSTRIDE_FS : LaneLayout<8>::FSTRIDE) * 8,
               lds4 = LaneLayout<4>::F * (P.fpost ? LaneLayout<4>::FSTRIDE_FS : LaneLayout<4>::FSTRIDE) * 8;
-    if (P.f32) return hipErrorInvalidValue;  // (no float32 form)
-    if (P.fpost && (P.K != 64 || (P.fp.beta && !P.fp_beta32g))) return hipErrorInvalidValue;
+    if (P.f32) return hipErrorInvalidValue;  // (float32 rows: pscl_launch_lane_fs_f32)
+    if (P.fpost &&(P.K != 64 || (P.fp.beta && !P.fp_beta32g))) return hipErrorInvalidValue;
     if (P.L == 8)
         if (P.fpost)
             hipLaunchKernelGGL((scl_lane_kernel<8, 1, true, false, true>), dim3((unsigned)grid), dim3(64), lds8, s, P);

@@ -26,6 +26,10 @@
 struct pscl_post_params {
     const double* llr;           // channel LLRs [.][N] (or [.][E] with rate matching)
     int N, n, K, W, rm_E;
+    // 1: llr points at float32 rows (the pscl_*_f32 DL-SCL calls set it per call): the launch goes to
+    // the float32 instances (dlscl_f32.hip).  As pscl_decode_params::f32 it fills what was padding: no
+    // member moves, so the float64 kernels' argument offsets and code stay as they were
+    int row_f32;
     const int32_t* rm_src;
     uint64_t info_mask[2];
     const int32_t* info_set;     // [K] (device)
@@ -84,7 +88,8 @@ struct pscl_decode_params {
     int rm_E;                    // NR rate matching: received length E (0 = none; llr is [B][E])
     // 1: llr points at float32 rows ([B][N] or [B][E] floats; the pscl_*_f32 entry points set it per
     // call): only the float32 instances may take the launch (pscl_launch_decode; scl128_lane_f32.hip,
-    // scl128_lane_rl_f32.hip, scl128_spec_f32.hip), every other kernel is refused.  It sits in what was
+    // scl128_lane_rl_f32.hip, scl128_spec_f32.hip, and for the forced-bit launches of a DL-SCL chain
+    // scl128_lane_fs_f32.hip, scl128_spec_fs_f32.hip), every other kernel is refused.  It sits in what was
     // the padding between rm_E and rm_src: no member moves and the block keeps its size, so the
     // kernels' argument offsets -- the hidden launch arguments behind the block among them -- and with
     // them the float64 instances' code stay as they were (static_assert below).
@@ -171,6 +176,10 @@ struct pscl_decode_params {
 
 static_assert(offsetof(pscl_decode_params, rm_src) == offsetof(pscl_decode_params, rm_E) + 8,
               "f32 fills the padding behind rm_E");
+// a DL-SCL call marks the rows of its decode launches here (its post passes: pscl_post_params::row_f32)
+inline void pscl_set_row_type(pscl_decode_params& P, bool f32) { P.f32 = f32 ? 1 : 0; }
+static_assert(offsetof(pscl_post_params, rm_src) == offsetof(pscl_post_params, rm_E) + 8,
+              "row_f32 fills the padding behind rm_E");
 
 #define PSCL_DL_NSEG 8     // 16-phase segments of N = 128: warm-start buckets
 #define PSCL_DL_CSTRIDE 16 // int32 stride of the bucket counters (one 64-byte line each)
@@ -204,6 +213,7 @@ __device__ __forceinline__ int64_t pscl_bucket_prefix(const int32_t* bcount, int
 struct pscl_replay_params {
     const double* llr;           // channel LLRs [.][N] (or [.][E] with rate matching)
     int N, n, K, W, rm_E;
+    int row_f32;                 // 1: llr points at float32 rows (pscl_post_params::row_f32; what was padding)
     const int32_t* rm_src;
     uint64_t info_mask[2];
     const int32_t* count;        // live entries (device)
@@ -213,6 +223,8 @@ struct pscl_replay_params {
     int bits_by_row;             // 1: bits row = act[entry]; 0: bits row = list position
     double* out;                 // [entries][K] decision LLRs (signed), row = entry
 };
+static_assert(offsetof(pscl_replay_params, rm_src) == offsetof(pscl_replay_params, rm_E) + 8,
+              "row_f32 fills the padding behind rm_E");
 
 // DL-SCL post pass of the long codes (N > PSCL_FAST_N, dlscl.hip dl_post_long_kernel): the
 // retry decodes run the HIST long kernel, whose best-path decision LLRs are the attempt's L0;
@@ -382,9 +394,12 @@ int pscl_lane_frames_per_wg(int L);
 hipError_t pscl_launch_lane(const pscl_decode_params& P, int64_t grid, hipStream_t s);
 hipError_t pscl_launch_lane_rowlist(const pscl_decode_params& P, int64_t grid, hipStream_t s);  // scl128_lane_rl.hip
 // the float32-row forms of the two (P.f32; scl128_lane_f32.hip, scl128_lane_rl_f32.hip) and of the exact
-// re-decode of the deferred rows (scl128_spec_f32.hip: the compiled-in codes at L = 4, 8, plain decodes)
+// decodes of the compiled-in codes at L = 4, 8 (scl128_spec_f32.hip: the plain re-decode of the deferred
+// rows; scl128_spec_fs_f32.hip: the forced-bit, warm-started retry rounds of a DL-SCL chain)
 hipError_t pscl_launch_lane_f32(const pscl_decode_params& P, int64_t grid, hipStream_t s);
 hipError_t pscl_launch_lane_rowlist_f32(const pscl_decode_params& P, int64_t grid, hipStream_t s);
+// the float32-row form of pscl_launch_lane_fs (scl128_lane_fs_f32.hip; no fused post pass)
+hipError_t pscl_launch_lane_fs_f32(const pscl_decode_params& P, int64_t grid, hipStream_t s);
 // 1: every launch of a plain decode of P's shape (screening, row list, exact re-decode) has a float32 form
 int pscl_f32_decode_available(const pscl_decode_params& P);
 // workgroups of a decode that adds its error counts with atomics (P.ref without P.cpart): each
@@ -440,6 +455,10 @@ hipError_t pscl_launch_iota64(int64_t* out, int64_t n, hipStream_t s);
 // stage[act[i]] = value, i < n (the three-stage decode: 3 over a retry chain's entry list)
 hipError_t pscl_launch_dl_mark_stage(const int64_t* act, int64_t n, uint8_t* stage, int value, hipStream_t s);
 hipError_t pscl_launch_replay(const pscl_replay_params& R, int64_t cap, hipStream_t s);
+// the float32-row forms of the replay and the post pass (dlscl_f32.hip); pscl_launch_replay and
+// pscl_launch_dl_post hand a launch with R.row_f32 / Q.row_f32 set to them
+hipError_t pscl_launch_replay_f32(const pscl_replay_params& R, int64_t cap, hipStream_t s);
+hipError_t pscl_launch_dl_post_f32(const pscl_post_params& Q, int64_t entries, hipStream_t s);
 hipError_t pscl_launch_tail_abs_scan(uint32_t lo, uint32_t hi, const uint64_t* exp_table, unsigned long long* out,
                                      hipStream_t s, int bits);
 hipError_t pscl_launch_softplus_tails(const double* v, int64_t n, const uint64_t* exp_table, double* exact,

@@ -604,8 +604,9 @@ static bool lane_long128(const pscl_decode_params& P) {
 int pscl_lane_long128_available(const pscl_decode_params& P) { return lane_long128(P) ? 1 : 0; }
 
 hipError_t pscl_launch_decode(const pscl_decode_params& P, int hist, hipStream_t s) {
-    // float32 rows (P.f32): the lane-per-path screening launch (plain or row list) and the exact
-    // compiled-in decode (pscl_launch_decode128) have float32 instances; every other kernel reads doubles
+    // float32 rows (P.f32): the lane-per-path screening launches (plain, row list, or the forced-bit
+    // retry round of a DL-SCL chain) and the exact compiled-in decode (pscl_launch_decode128: plain or
+    // forced-bit) have float32 instances; every other kernel reads doubles
     if (P.f32 && (hist || P.long_mode || !P.fast || !pscl_f32_decode_available(P))) return hipErrorInvalidValue;
     if (P.long_mode) {
         if (!hist && P.apx) return pscl_launch_lane_long(P, s);  // (screening: lane-per-path only)
@@ -621,12 +622,14 @@ hipError_t pscl_launch_decode(const pscl_decode_params& P, int hist, hipStream_t
         return P.f32 ? pscl_launch_lane_f32(P, g < 1 ? 1 : (g > cap ? cap : g), s)
                      : pscl_launch_lane(P, g < 1 ? 1 : (g > cap ? cap : g), s);
     }
-    if (P.f32 && (P.apx || P.force || P.lane_exact)) return hipErrorInvalidValue;  // (the exact plain decode is what is left)
+    if (P.f32 && P.fpost) return hipErrorInvalidValue;  // (the fused post pass reads the row as doubles)
     if (!hist && pscl_lane_fs_available(P)) {  // (P.B: the round's entry capacity)
         const int fw = pscl_lane_frames_per_wg(P.L);
         const int64_t g = (P.B + fw - 1) / fw;
-        return pscl_launch_lane_fs(P, g < 1 ? 1 : (g > (1 << 20) ? (1 << 20) : g), s);
+        return P.f32 ? pscl_launch_lane_fs_f32(P, g < 1 ? 1 : (g > (1 << 20) ? (1 << 20) : g), s)
+                     : pscl_launch_lane_fs(P, g < 1 ? 1 : (g > (1 << 20) ? (1 << 20) : g), s);
     }
+    if (P.f32 && (P.apx || P.lane_exact)) return hipErrorInvalidValue;  // (the exact compiled-in decode is what is left)
     if (!hist && lane_long128(P)) return pscl_launch_lane_long(P, s);
     if (!hist && pscl_lane_exact_available(P)) return pscl_launch_lane_exact(P, s);
     if (pscl_decode_wpg(P) < 1) return hipErrorInvalidValue;

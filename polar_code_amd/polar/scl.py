@@ -265,6 +265,104 @@ class SCLDecoder:
             d_counters=counters.data_ptr() if counters is not None else 0)
         return best, flags, stage
 
+    # ---- DL-SCL on tensors: the retry chains after a list decode, an adaptive decode or the caller's baseline
+    def _dl_call(self, llr, name):
+        """The float64 or float32 form of the native DL-SCL call `name` for llr (validated first), the
+        rows it takes and whether they are a widened temporary: float32 rows natively where
+        native.f32_available(), else widened with llr.double() (see decode_tensor)."""
+        f32 = self._f32_rows(llr, self._dec.E or self.N)
+        if f32 and self._dec.f32_available():
+            return getattr(self._dec, name + "_f32"), llr, False
+        return getattr(self._dec, name), (llr.double() if f32 else llr), f32
+
+    def _dl_outputs(self, llr, retries: int):
+        import torch
+
+        B, rounds = llr.shape[0], max(0, min(int(retries), self.K)) if self._dec.crc_deg else 0
+        attempts = torch.empty((B,), dtype=torch.int32, device=llr.device)
+        tried = torch.empty((B, rounds), dtype=torch.int32, device=llr.device)
+        return attempts, tried, dict(d_attempts=attempts.data_ptr(), d_tried=tried.data_ptr() if rounds else 0,
+                                     tried_stride=rounds)
+
+    def decode_tensor_dlscl(self, llr, retries: int, beta=None, ref_words=None, k_payload: int = 0, counters=None):
+        """SCL + DL-SCL retries (pscl_dlscl_device; flip.py:65-141 per frame) on the caller's current
+        torch stream: llr is a contiguous float64 or float32 [B, N] (or [B, E]) tensor on this GPU,
+        beta the [K, K] flip metric matrix or None (rank by |L0|).  Returns (best_words [B, W] int64,
+        flags [B] uint8, attempts [B] int32 = 1 + flips tried, tried [B, min(retries, K)] int32 = the
+        flip indices in order, -1 padded).  With ref_words the baseline's statistics are added into
+        counters[0] and the final outputs' into counters[1] (`counters`: int64 [2, 8] tensor).
+        float32 rows: pscl_dlscl_device_f32 where native.f32_available(), else widened with
+        llr.double(); either way the result is the float64 result on the widened rows.  On a
+        pipelined handle the retry chains are deferred: native.join() orders them back."""
+        import torch
+
+        call, rows, widened = self._dl_call(llr, "dlscl_device")
+        B, W = rows.shape[0], self._dec.W
+        best = torch.empty((B, W), dtype=torch.int64, device=rows.device)
+        flags = torch.empty((B,), dtype=torch.uint8, device=rows.device)
+        attempts, tried, out = self._dl_outputs(rows, retries)
+        self._dec.set_stream(torch.cuda.current_stream(rows.device).cuda_stream)
+        call(rows.data_ptr(), B, int(retries), beta=beta, d_best=best.data_ptr(), d_flags=flags.data_ptr(), **out,
+             d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
+             d_counters_scl=counters.data_ptr() if counters is not None else 0,
+             d_counters_dl=counters.data_ptr() + 8 * _native.PSCL_NCOUNT if counters is not None else 0)
+        if widened:
+            self._dec.join()  # (the widened temporary: see decode_tensor)
+        return best, flags, attempts, tried
+
+    def decode_tensor_retry(self, llr, best, flags, retries: int, beta=None, stage=None, ref_words=None,
+                            k_payload: int = 0, counters=None):
+        """DL-SCL retry rounds on a baseline the caller holds (pscl_retry_device): `best` [B, W] int64
+        and `flags` [B] uint8 are what this decoder's list decode left (decode_tensor, the adaptive and
+        staged methods); the frames without the CRC-pass bit enter the chains, and best, flags and
+        `stage` ([B] uint8 or None: 3 at those frames) are updated in place.  Returns (attempts [B]
+        int32, tried [B, min(retries, K)] int32).  With ref_words the final outputs' statistics are
+        added into `counters` (int64[8] tensor).  float32 rows as decode_tensor_dlscl."""
+        import torch
+
+        call, rows, widened = self._dl_call(llr, "retry_device")
+        B, W = rows.shape[0], self._dec.W
+        if (best.dtype != torch.int64 or not best.is_contiguous() or tuple(best.shape) != (B, W)
+                or flags.dtype != torch.uint8 or not flags.is_contiguous() or tuple(flags.shape) != (B,)
+                or (stage is not None and (stage.dtype != torch.uint8 or not stage.is_contiguous()
+                                           or tuple(stage.shape) != (B,)))):
+            raise ValueError("best must be a contiguous int64 [B, W] tensor, flags and stage contiguous uint8 [B]")
+        attempts, tried, out = self._dl_outputs(rows, retries)
+        self._dec.set_stream(torch.cuda.current_stream(rows.device).cuda_stream)
+        call(rows.data_ptr(), B, int(retries), beta=beta, d_best=best.data_ptr(), d_flags=flags.data_ptr(),
+             d_stage=stage.data_ptr() if stage is not None else 0, **out,
+             d_ref=ref_words.data_ptr() if ref_words is not None else 0, k_payload=k_payload,
+             d_counters_dl=counters.data_ptr() if counters is not None else 0)
+        if widened:
+            self._dec.join()  # (the widened temporary: see decode_tensor)
+        return attempts, tried
+
+    def decode_tensor_adaptive_dlscl(self, llr, retries: int, beta=None, ref_words=None, k_payload: int = 0,
+                                     counters=None):
+        """The three-stage decode (pscl_adaptive_dlscl_device): SC, the list decoder where SC fails the
+        CRC, DL-SCL flips where the list decoder fails it too, on the caller's current torch stream.
+        Returns (best_words [B, W] int64, flags [B] uint8, stage [B] uint8 = 1, 2 or 3, attempts [B]
+        int32, tried [B, min(retries, K)] int32, n_escalated [1] int32).  With ref_words the
+        statistics are added into `counters` (int64 [3, 8] tensor: SC, adaptive, final).  float32 rows
+        as decode_tensor_dlscl (pscl_adaptive_dlscl_device_f32 where native.f32_available())."""
+        import torch
+
+        call, rows, widened = self._dl_call(llr, "adaptive_dlscl_device")
+        B, W = rows.shape[0], self._dec.W
+        best = torch.empty((B, W), dtype=torch.int64, device=rows.device)
+        flags = torch.empty((B,), dtype=torch.uint8, device=rows.device)
+        stage = torch.empty((B,), dtype=torch.uint8, device=rows.device)
+        n_esc = torch.zeros((1,), dtype=torch.int32, device=rows.device)
+        attempts, tried, out = self._dl_outputs(rows, retries)
+        self._dec.set_stream(torch.cuda.current_stream(rows.device).cuda_stream)
+        call(rows.data_ptr(), B, int(retries), beta=beta, d_best=best.data_ptr(), d_flags=flags.data_ptr(),
+             d_stage=stage.data_ptr(), **out, d_ref=ref_words.data_ptr() if ref_words is not None else 0,
+             k_payload=k_payload, d_counters=counters.data_ptr() if counters is not None else 0,
+             d_n_escalated=n_esc.data_ptr())
+        if widened:
+            self._dec.join()  # (the widened temporary: see decode_tensor)
+        return best, flags, stage, attempts, tried, n_esc
+
     # ---- caller payloads: payload -> CRC -> codeword (-> symbols or AWGN LLR rows) on the device
     def encode(self, payload_bits: np.ndarray, device=None) -> dict:
         """payload_bits [B, k_payload] 0/1 (k_payload = K - CRC degree) -> dict(msg [B, K] int8 =
