@@ -220,6 +220,55 @@ int pscl_uncoded_device(pscl_handle* h, uint64_t seed, uint32_t stream_id, doubl
 int pscl_set_rate_match(pscl_handle* h, int E);
 
 /*
+ * The front end above as a pass of its own, on a handle with pscl_set_rate_match(h, E), E > 0:
+ *   d_llr [B][E] float64 received LLRs (rows 8-byte aligned, nothing more; odd E is legal)
+ *   d_out [B][N] float64: the decoder-internal rows, subblock_deinterleave(derate_match_polar(row, N), N)
+ *         (scl_nr.py:47-48), bit for bit what the decode kernels' fused staging computes: repeats summed
+ *         in index order, then 0.0 + s (a -0 sum becomes +0), then the remainder copy, then one division
+ *         by the count; E <= N pads with -1.0.  A plain handle (same N, information set, L, CRC) decodes
+ *         d_out to the results the rate-matched handle gives on d_llr.
+ * One kernel on the handle's stream, no host wait; pending pipelined work is ordered first.  Every N
+ * and E pscl_set_rate_match accepts (only the N-vector is staged on chip, never the E-row).  B = 0
+ * returns PSCL_OK without a launch.  PSCL_EINVAL for a NULL handle, B < 0, a NULL pointer with B > 0
+ * and a handle without rate matching; PSCL_EUNSUP for B above 2^31 - 1, what one launch covers.
+ */
+int pscl_derate_match_device(pscl_handle* h, const double* d_llr, int64_t B, double* d_out);
+
+/*
+ * Staged de-rate-matching (default off).  With enable = 1 and rate matching on, four calls run the
+ * pass above once into handle scratch and then the plain-row screening and SC kernels on its rows,
+ * where today they refuse a rate-matched handle or fall back to the exact kernels alone:
+ *   pscl_decode_device   plain calls (no forced bits, metrics, candidates, decision LLRs) whose
+ *                        rate-matching-free twin (same N, information set, L, CRC, screening setting)
+ *                        takes a screening kernel -- run-time sets at N = 128 .. 1024, L = 4 .. 32, and
+ *                        the compiled-in (128,64) code: the pass, the twin's screening kernel on its
+ *                        rows, and the exact re-decode of the deferred frames on the caller's rows, as
+ *                        without the mode.  A handle with a rate-matched screening kernel of its own
+ *                        (the compiled-in (128,88) code, L = 4, 8) keeps it, and a twin that is exact
+ *                        anyway (L <= 2, N < 128, screening off) keeps today's path.
+ *   pscl_sc_device       N = 32, 64, 256, 512, 1024: the pass, then the SC kernel (no PSCL_EUNSUP);
+ *                        N = 128 keeps its fused kernel.
+ *   pscl_escalate_device its dense gathered batch as pscl_decode_device.
+ *   pscl_adaptive_async_device  N = 32 .. 1024 (no PSCL_EUNSUP): one pass, the SC stage on its rows,
+ *                        stage 2's row-list screening decode on the same rows by row index, the exact
+ *                        re-decode (or, where the twin's stage 2 is exact, stage 2 itself) on the
+ *                        caller's rows.  On a pipelined handle the staged rows alternate two parities
+ *                        with the list and count scratch.  A (128,88) handle at L = 4, 8 keeps today's path.
+ * No other call consults the mode: the _f32 forms, the DL-SCL calls, pscl_retry_device,
+ * pscl_adaptive_device, pscl_simulate*, pscl_decode and pscl_path_llrs_device behave as with it off.
+ * Every output, counter and pscl_screening_count is bit-identical to the mode-off call on the same
+ * rows.  The scratch grows to the largest B seen; a later call of the same size allocates nothing.
+ * The setter orders pending pipelined work first; it may precede or follow pscl_set_rate_match and
+ * has no effect while rate matching is off.
+ *
+ * pscl_rm_staged_stats: passes launched by those four calls and the rows they staged since the handle
+ * was created (or the last reset = 1) -- the outputs being identical, the only sign that the staged
+ * route ran.  pscl_derate_match_device is not counted.  Either pointer may be NULL.
+ */
+int pscl_set_rate_match_staged(pscl_handle* h, int enable);
+int pscl_rm_staged_stats(pscl_handle* h, int64_t* passes, int64_t* rows, int reset);
+
+/*
  * Decision LLRs of given paths (scl.py:158,166 info_llrs of a path whose bits are known):
  * for frame b with information bits d_bits[b] (frozen bits 0), the leaf LLR at every
  * information phase, recomputed top-down through the same f/g operations as the decoder
@@ -299,7 +348,8 @@ int pscl_adaptive_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
  * results' statistics are added into d_counters as pscl_decode_device adds them (the SC baseline
  * curve).  Pending pipelined work is ordered first.
  *   N = 32, 64, 256, 512, 1024: plain rows of N LLRs.  N = 128: plain and rate-matched rows.
- * PSCL_EUNSUP for N < 32, and for a rate-matched handle with N != 128.
+ * PSCL_EUNSUP for N < 32, and for a rate-matched handle with N != 128 (unless
+ * pscl_set_rate_match_staged is on: the de-rate-matching pass then runs first).
  *
  * pscl_escalate_device: for every frame whose d_flags lacks PSCL_FLAG_CRC_PASS, d_best / d_flags
  * become exactly pscl_decode_device's outputs for that frame and d_stage 2; the other frames are
@@ -339,7 +389,8 @@ int pscl_escalate_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_
  * entry point on the handle, or the second following pipelined call; consecutive pipelined calls
  * must not write the same output buffers.  Results are bit-identical to the non-pipelined form.
  * PSCL_EINVAL without a CRC, for B < 0, for d_ref without d_counters and for a missing d_llr /
- * d_best / d_flags; PSCL_EUNSUP for N < 32, rate matching at N != 128 and B > 2^31 - 1.
+ * d_best / d_flags; PSCL_EUNSUP for N < 32, rate matching at N != 128 (unless
+ * pscl_set_rate_match_staged is on) and B > 2^31 - 1.
  */
 int pscl_adaptive_async_device(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags,
                                uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,

@@ -51,6 +51,7 @@ EXPORTS = (
     "pscl_adaptive_async_device_f32",
     "pscl_dlscl_device_f32", "pscl_retry_device_f32", "pscl_adaptive_dlscl_device_f32", "pscl_path_llrs_device_f32",
     "pscl_encode_device", "pscl_channel_payload_device", "pscl_encode_cpu",
+    "pscl_derate_match_device", "pscl_set_rate_match_staged", "pscl_rm_staged_stats",
 )
 
 # pscl_set_tuning knobs (include/polar_scl.h)
@@ -173,6 +174,9 @@ def lib() -> C.CDLL:
         "pscl_timing_read": (C.c_int, [_vp, P(_i64), P(_dbl)]),
         "pscl_launch_info": (C.c_int, [_vp, _i64, P(C.c_int), P(_i64), P(C.c_int)]),
         "pscl_set_rate_match": (C.c_int, [_vp, C.c_int]),
+        "pscl_derate_match_device": (C.c_int, [_vp, _vp, _i64, _vp]),
+        "pscl_set_rate_match_staged": (C.c_int, [_vp, C.c_int]),
+        "pscl_rm_staged_stats": (C.c_int, [_vp, P(_i64), P(_i64), C.c_int]),
         "pscl_set_beta": (C.c_int, [_vp, _vp]),
         "pscl_path_llrs_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
         "pscl_uncoded_device": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, C.c_int, _i64, _i64, _vp]),
@@ -257,6 +261,24 @@ class Decoder:
         """NR: decode inputs become [B, E] received LLRs (de-rate-match + de-interleave on GPU)."""
         check(lib().pscl_set_rate_match(self._h, int(E)))
         self.E = int(E)
+
+    def set_rate_match_staged(self, on: bool = True) -> None:
+        """Staged de-rate-matching (pscl_set_rate_match_staged, default off): decode_device, sc_device,
+        escalate_device and adaptive_async_device of a rate-matched handle run the de-rate-matching
+        pass once and then the plain-row screening and SC kernels; results are bit-identical."""
+        check(lib().pscl_set_rate_match_staged(self._h, 1 if on else 0))
+
+    def derate_match_device(self, d_llr: int, B: int, d_out: int) -> None:
+        """[B][E] received LLRs -> the [B][N] decoder-internal rows, enqueued without a host wait
+        (pscl_derate_match_device; a rate-matched handle)."""
+        with self._lock:
+            check(lib().pscl_derate_match_device(self._h, d_llr or None, int(B), d_out or None))
+
+    def rm_staged_stats(self, reset: bool = False) -> dict:
+        """Passes the staged mode launched and the rows they staged (pscl_rm_staged_stats)."""
+        a, b = _i64(), _i64()
+        check(lib().pscl_rm_staged_stats(self._h, C.byref(a), C.byref(b), 1 if reset else 0))
+        return {"passes": int(a.value), "rows": int(b.value)}
 
     @property
     def _h(self):

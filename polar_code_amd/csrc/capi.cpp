@@ -209,6 +209,14 @@ struct pscl_handle {
     int ad_par = 0;
     int64_t n_regrow = 0;  // scratch buffers freed and regrown (each drains the side streams on the host)
     int64_t n_ad_screened = 0, n_ad_exact = 0, n_ad_waits = 0;  // pscl_adaptive_stats
+    // staged de-rate-matching (pscl_set_rate_match_staged): pscl_decode_device, pscl_sc_device,
+    // pscl_escalate_device and pscl_adaptive_async_device write a rate-matched batch's decoder-internal
+    // rows once (derate.hip) and run the plain-row screening and SC kernels on them.  Scratch slot
+    // kRmSlot holds the rows of the stream-ordered calls -- read only by launches on the handle's
+    // stream, so one buffer serves a pipelined plain decode of any depth -- and kRmAdSlot[q] those of
+    // an adaptive call of parity q, which its stage 2 reads on a side stream
+    bool rm_staged = false;
+    int64_t n_rm_passes = 0, n_rm_rows = 0;  // pscl_rm_staged_stats
 };
 
 namespace {
@@ -403,11 +411,54 @@ const char* f32_unsupported(const pscl_handle* h) {
     return nullptr;
 }
 
+constexpr int kRmSlot = 142, kRmAdSlot[2] = {143, 144};
+
+// the de-rate-matching pass (derate.hip) of B rate-matched rows on stream st: d_out, or (null) scratch
+// slot `slot`, grown to the largest B seen; *rows gets where the [B][N] rows are.  count: one of the
+// staged mode's passes (pscl_rm_staged_stats)
+int launch_derate(pscl_handle* h, const double* d_llr, int64_t B, double* d_out, int slot, hipStream_t st, bool count,
+                  const double** rows) {
+    if (B > PSCL_DERATE_MAX_B) return fail(PSCL_EUNSUP, "B exceeds the %lld rows of one de-rate-matching launch", PSCL_DERATE_MAX_B);
+    if (!d_out) {
+        void* d;
+        const int rc = ensure(h, slot, (size_t)B * (size_t)h->N * 8, &d);
+        if (rc) return rc;
+        d_out = (double*)d;
+    }
+    pscl_derate_params D;
+    memset(&D, 0, sizeof(D));
+    D.llr = d_llr;
+    D.out = d_out;
+    D.B = B;
+    D.n = h->n;
+    D.E = h->rm_E;
+    const hipError_t e = pscl_launch_derate(D, st);
+    if (e != hipSuccess) return fail(PSCL_EDEVICE, "de-rate-matching launch: %s", hipGetErrorString(e));
+    if (count) {
+        h->n_rm_passes++;
+        h->n_rm_rows += B;
+    }
+    if (rows) *rows = d_out;
+    return PSCL_OK;
+}
+
+// the handle's rate-matching-free twin in a block: P on plain rows (layout recomputed)
+void plain_twin(pscl_decode_params& P, const double* rows, int hist) {
+    P.llr = rows;
+    P.rm_E = 0;
+    P.rm_src = nullptr;
+    pscl_decode_layout(P, hist);
+}
+
 // tail (a pipelined DL-SCL baseline, tail_par its scratch parity): the re-decode of the deferred
 // frames goes to tail after the screening pass, and the call returns; the caller queues the rest of
 // the baseline's tail there and marks it with ev_tail[tail_par]
+// rm_stage (pscl_decode_device and pscl_escalate_device on a staged handle): a plain decode of
+// rate-matched rows that has no screening kernel of its own, but whose rate-matching-free twin has,
+// runs the de-rate-matching pass into scratch and the twin's screening kernel on those rows; the exact
+// re-decode of the deferred frames reads the caller's rows with rm_E, as without the mode
 int launch_decode(pscl_handle* h, const pscl_decode_params& P0, int hist, hipStream_t st = nullptr, int scr_slot = 38,
-                  bool pipe = false, hipStream_t tail = nullptr, int tail_par = 0) {
+                  bool pipe = false, hipStream_t tail = nullptr, int tail_par = 0, bool rm_stage = false) {
     if (!st) st = h->stream;
     pscl_decode_params P = P0;
     if (P.long_mode) {  // global scratch of every workgroup in flight (scl_long.hip)
@@ -437,10 +488,18 @@ int launch_decode(pscl_handle* h, const pscl_decode_params& P0, int hist, hipStr
     pscl_decode_params T = P;
     T.apx = 1;
     const int64_t lx = h->tune[PSCL_TUNE_LANE_EXACT];  // the exact lane-per-path instance (knob 3: every frame)
-    const bool screen = h->screen && lx != 3 && !hist && !P.metrics && !P.cands && !P.force && !P.sc_hard && !P.fidx &&
-                        !P.d_count &&
-                        (P.fast ? (pscl_screening_available(P) != 0 || pscl_lane_long128_available(T) != 0)
-                                : pscl_lane_long_available(T) != 0);
+    const bool plain = h->screen && lx != 3 && !hist && !P.metrics && !P.cands && !P.force && !P.sc_hard && !P.fidx &&
+                       !P.d_count;
+    bool screen = plain && (P.fast ? (pscl_screening_available(P) != 0 || pscl_lane_long128_available(T) != 0)
+                                   : pscl_lane_long_available(T) != 0);
+    bool staged = false;
+    if (rm_stage && plain && !screen && h->rm_staged && P.rm_E && !P.f32 && !tail) {
+        pscl_decode_params T2 = T;
+        plain_twin(T2, nullptr, hist);
+        staged = T2.fast ? (pscl_screening_available(T2) != 0 || pscl_lane_long128_available(T2) != 0)
+                         : pscl_lane_long_available(T2) != 0;
+        screen = staged;
+    }
     hipError_t err;
     if (!(screen && pipe)) {
         const int rc = join_pipe(h, 1);
@@ -478,6 +537,11 @@ int launch_decode(pscl_handle* h, const pscl_decode_params& P0, int hist, hipStr
         HIP_TRY(hipMemsetAsync(d_cnt, 0, 4, st));
         pscl_decode_params S = P;
         S.apx = 1;
+        if (staged) {  // the pass, then the twin's screening kernel on its rows
+            const double* rows;
+            if ((rc = launch_derate(h, P.llr, P.B, nullptr, kRmSlot, st, true, &rows))) return rc;
+            plain_twin(S, rows, hist);
+        }
         pscl_decode_layout(S, hist);  // (no exp table in LDS)
         S.amb_list = (int64_t*)d_list;
         S.amb_count = (int32_t*)d_cnt;
@@ -874,7 +938,7 @@ int decode_device_impl(pscl_handle* h, const void* d_llr, bool f32, int64_t B, c
     if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
     if (!h->pipelined && (rc = join_pipe(h))) return rc;
     if (h->pipelined && (h->ad_pending[0] || h->ad_pending[1]) && (rc = join_pipe(h, 1))) return rc;  // (adaptive calls' stage 2)
-    return launch_decode(h, P, hist, nullptr, 38, h->pipelined);
+    return launch_decode(h, P, hist, nullptr, 38, h->pipelined, nullptr, 0, !f32);
 }
 }  // namespace
 
@@ -898,8 +962,10 @@ namespace {
 // the SC stage over all B frames as one launch on the handle's stream (sc128_lane.hip at N = 128,
 // sc_lane.hip at the other lengths), timed like a decode when timing is on
 // f32: d_llr points at float32 rows (N = 128 only; the callers check)
+// plain_rows: d_llr points at rows of N values whatever the handle's rate matching (the staged mode:
+// the de-rate-matching pass wrote them)
 int launch_sc_stage(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags, uint8_t* d_stage,
-                    bool f32 = false) {
+                    bool f32 = false, bool plain_rows = false) {
     hipStream_t s = h->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->timing) {  // (the SC launch is one timed launch on the handle's stream, like a decode)
@@ -927,15 +993,15 @@ int launch_sc_stage(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_
         S.info_mask[1] = h->info_mask[1];
         S.epi_table = h->d_epi;
         S.epi_words = h->epi_words;
-        S.rm_E = h->rm_E;
-        S.rm_src = h->d_rm_src;
+        S.rm_E = plain_rows ? 0 : h->rm_E;
+        S.rm_src = plain_rows ? nullptr : h->d_rm_src;
         S.best = d_best;
         S.flags = d_flags;
         S.stage = d_stage;
         e = f32 ? pscl_launch_sc_lane_f32(S, s) : pscl_launch_sc_lane(S, s);
     } else {
         if (f32) return fail(PSCL_EUNSUP, "float32 rows: the SC stage takes N = %d only (N = %d)", PSCL_FAST_N, h->N);
-        if (!pscl_scn_lane_available(h->N) || h->rm_E)
+        if (!pscl_scn_lane_available(h->N) || (h->rm_E && !plain_rows))
             return fail(PSCL_EUNSUP, "no SC kernel for N = %d%s", h->N, h->rm_E ? " with rate matching" : "");
         pscl_scn_params S;
         memset(&S, 0, sizeof(S));
@@ -963,8 +1029,9 @@ int launch_sc_stage(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_
 // and scattered back; d_stage (or null) gets 2 at those frames.  Scratch slots 72..76: count, frame
 // list, dense rows, dense best words, dense flags.  One host wait: the count sizes the dense batch.
 // f32: d_llr points at float32 rows, widened while they are gathered; the dense batch is doubles
+// rm_stage: the dense batch may take the staged de-rate-matching route (launch_decode)
 int escalate_failed(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_best, uint8_t* d_flags, uint8_t* d_stage,
-                    int64_t* n_out, bool f32 = false) {
+                    int64_t* n_out, bool f32 = false, bool rm_stage = false) {
     const int W = h->W;
     const int64_t row = h->rm_E ? h->rm_E : h->N;
     hipStream_t s = h->stream;
@@ -999,7 +1066,7 @@ int escalate_failed(pscl_handle* h, const double* d_llr, int64_t B, uint64_t* d_
         P.best = (uint64_t*)d_b2;
         P.flags = (uint8_t*)d_f2;
         if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
-        if ((rc = launch_decode(h, P, 0))) return rc;
+        if ((rc = launch_decode(h, P, 0, nullptr, 38, false, nullptr, 0, rm_stage))) return rc;
         if ((e = pscl_launch_scatter_results((const int64_t*)d_act, n, W, (const uint64_t*)d_b2, (const uint8_t*)d_f2, d_best,
                                              d_flags, s)) != hipSuccess)
             return fail(PSCL_EDEVICE, "scatter launch: %s", hipGetErrorString(e));
@@ -1057,7 +1124,8 @@ int sc_device_impl(pscl_handle* h, const double* d_llr, bool f32, int64_t B, uin
     if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
     if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
     if (h->N < 32) return fail(PSCL_EUNSUP, "the SC stage is implemented for N = 32 .. %d (N = %d)", PSCL_MAX_N, h->N);
-    if (h->rm_E && h->N != PSCL_FAST_N)
+    const bool stage = h->rm_staged && h->rm_E && !f32 && h->N != PSCL_FAST_N;  // (the staged mode: the pass first)
+    if (h->rm_E && h->N != PSCL_FAST_N && !stage)
         return fail(PSCL_EUNSUP, "the SC stage takes rate-matched rows at N = %d only (N = %d)", PSCL_FAST_N, h->N);
     if (f32 && h->N != PSCL_FAST_N)
         return fail(PSCL_EUNSUP, "float32 rows: the SC stage takes N = %d only (N = %d)", PSCL_FAST_N, h->N);
@@ -1065,7 +1133,8 @@ int sc_device_impl(pscl_handle* h, const double* d_llr, bool f32, int64_t B, uin
     if (!d_llr || !d_best || !d_flags) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
     int rc = enter(h);  // (pending pipelined work first)
     if (rc) return rc;
-    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage, f32))) return rc;
+    if (stage && (rc = launch_derate(h, d_llr, B, nullptr, kRmSlot, h->stream, true, &d_llr))) return rc;
+    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage, f32, stage))) return rc;
     return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, 0);
 }
 }  // namespace
@@ -1099,7 +1168,7 @@ int escalate_device_impl(pscl_handle* h, const double* d_llr, bool f32, int64_t 
     int rc = enter(h);
     if (rc) return rc;
     int64_t n = 0;
-    if ((rc = escalate_failed(h, d_llr, B, d_best, d_flags, d_stage, &n, f32))) return rc;
+    if ((rc = escalate_failed(h, d_llr, B, d_best, d_flags, d_stage, &n, f32, !f32))) return rc;
     if (n_escalated) *n_escalated = n;
     return count_final(h, d_best, d_flags, B, d_ref, k_payload, d_counters, n);
 }
@@ -1157,9 +1226,12 @@ int adaptive_begin(pscl_handle* h, bool pipe, int* par) {
 // pipe: everything after the compaction on parity q's side stream behind ev_adc[q]; ev_ad[q] marks its end.
 // f32: d_llr points at float32 rows (a handle with float32 kernels, f32_unsupported; the callers check):
 // the row-list launch and the exact re-decode are the float32 instances
+// d_stg (the staged mode, or null): the call's rows de-rate-matched by the pass, [B][N].  The row-list
+// screening launch is then the rate-matching-free twin's and reads d_stg by the same row indices (no
+// second pass, no gather); the exact kernel reads the caller's rows with rm_E, as without the mode
 int adaptive_escalate_enqueue(pscl_handle* h, int q, bool pipe, const double* d_llr, int64_t B, uint64_t* d_best,
                               uint8_t* d_flags, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
-                              int32_t* d_n_escalated, bool f32 = false) {
+                              int32_t* d_n_escalated, bool f32 = false, const double* d_stg = nullptr) {
     hipStream_t s = h->stream;
     const int base = kAdSlot[q];
     const int64_t regrown = h->n_regrow;
@@ -1184,6 +1256,7 @@ int adaptive_escalate_enqueue(pscl_handle* h, int q, bool pipe, const double* d_
     if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
     pscl_decode_params S = P;  // the row-list screening launch
     S.apx = 1;
+    if (d_stg) plain_twin(S, d_stg, 0);
     pscl_decode_layout(S, 0);
     S.amb_list = (int64_t*)d_amb;
     S.amb_count = amb_cnt;
@@ -1238,13 +1311,15 @@ int adaptive_escalate_enqueue(pscl_handle* h, int q, bool pipe, const double* d_
 }
 
 // the argument checks the adaptive calls without a host wait share
-int adaptive_async_args(pscl_handle* h, int64_t B, int k_payload) {
+// staged: the caller consults the staged mode (pscl_adaptive_async_device), which lifts the refusal
+// of rate-matched rows at N != 128
+int adaptive_async_args(pscl_handle* h, int64_t B, int k_payload, bool staged = false) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
     if (!h->crc_poly) return fail(PSCL_EINVAL, "adaptive decoding needs a CRC (without one every SC result passes)");
     if (k_payload < 0 || k_payload > h->K) return fail(PSCL_EINVAL, "k_payload out of range");
     if (h->N < 32) return fail(PSCL_EUNSUP, "the SC stage is implemented for N = 32 .. %d (N = %d)", PSCL_MAX_N, h->N);
-    if (h->rm_E && h->N != PSCL_FAST_N)
+    if (h->rm_E && h->N != PSCL_FAST_N && !(staged && h->rm_staged))
         return fail(PSCL_EUNSUP, "the SC stage takes rate-matched rows at N = %d only (N = %d)", PSCL_FAST_N, h->N);
     if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
     return PSCL_OK;
@@ -1253,10 +1328,30 @@ int adaptive_async_args(pscl_handle* h, int64_t B, int k_payload) {
 }  // namespace
 
 namespace {
+// does pscl_adaptive_async_device take the staged route on this handle: always at N != 128 (the SC
+// kernels of those lengths take plain rows only), and at N = 128 where the twin's stage 2 has a
+// row-list screening kernel and the handle's own has none (the compiled (128,88) code keeps its own)
+bool adaptive_stages(const pscl_handle* h) {
+    if (!h->rm_staged || !h->rm_E) return false;
+    if (h->N != PSCL_FAST_N) return true;
+    if (!h->screen || h->tune[PSCL_TUNE_LANE_EXACT] == 3) return false;
+    pscl_decode_params S;
+    fill_decode_params(h, S, 0);
+    S.apx = 1;
+    S.B = 1;
+    S.fidx = S.amb_list = reinterpret_cast<int64_t*>(16);  // (a row-list launch's shape; nothing is launched)
+    S.d_count = S.amb_count = reinterpret_cast<int32_t*>(16);
+    S.out_by_row = 1;
+    pscl_decode_layout(S, 0);
+    if (pscl_lane_available(S) != 0 || pscl_lane_long128_available(S) != 0) return false;
+    plain_twin(S, nullptr, 0);
+    return pscl_lane_available(S) != 0 || pscl_lane_long128_available(S) != 0;
+}
+
 int adaptive_async_impl(pscl_handle* h, const double* d_llr, bool f32, int64_t B, uint64_t* d_best, uint8_t* d_flags,
                         uint8_t* d_stage, const uint64_t* d_ref, int k_payload, int64_t* d_counters,
                         int32_t* d_n_escalated) {
-    int rc = adaptive_async_args(h, B, k_payload);
+    int rc = adaptive_async_args(h, B, k_payload, !f32);
     if (rc) return rc;
     if (d_ref && !d_counters) return fail(PSCL_EINVAL, "d_ref given without d_counters");
     if (B > 0 && (!d_llr || !d_best || !d_flags)) return fail(PSCL_EINVAL, "d_llr, d_best and d_flags are required");
@@ -1272,8 +1367,17 @@ int adaptive_async_impl(pscl_handle* h, const double* d_llr, bool f32, int64_t B
     }
     int q = 0;
     if ((rc = adaptive_begin(h, pipe, &q))) return rc;
-    if ((rc = launch_sc_stage(h, d_llr, B, d_best, d_flags, d_stage, f32))) return rc;
-    return adaptive_escalate_enqueue(h, q, pipe, d_llr, B, d_best, d_flags, d_ref, k_payload, d_counters, d_n_escalated, f32);
+    // the staged mode: one pass into parity q's rows (adaptive_begin has ordered the handle's stream
+    // behind the parity's previous stage 2, which read them), the SC stage and stage 2's screening on those
+    const double* d_stg = nullptr;
+    if (!f32 && adaptive_stages(h)) {
+        const int64_t regrown = h->n_regrow;
+        if ((rc = launch_derate(h, d_llr, B, nullptr, kRmAdSlot[q], h->stream, true, &d_stg))) return rc;
+        h->n_ad_waits += h->n_regrow - regrown;
+    }
+    if ((rc = launch_sc_stage(h, d_stg ? d_stg : d_llr, B, d_best, d_flags, d_stage, f32, d_stg != nullptr))) return rc;
+    return adaptive_escalate_enqueue(h, q, pipe, d_llr, B, d_best, d_flags, d_ref, k_payload, d_counters, d_n_escalated, f32,
+                                     d_stg);
 }
 }  // namespace
 
@@ -2828,6 +2932,35 @@ int pscl_set_rate_match(pscl_handle* h, int E) {
     const int rc = enter(h);
     if (rc) return rc;
     h->rm_E = E;
+    return PSCL_OK;
+}
+
+int pscl_derate_match_device(pscl_handle* h, const double* d_llr, int64_t B, double* d_out) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
+    if (!h->rm_E) return fail(PSCL_EINVAL, "the handle has no rate matching (pscl_set_rate_match)");
+    if (B > 0 && (!d_llr || !d_out)) return fail(PSCL_EINVAL, "d_llr and d_out are required");
+    if (B > PSCL_DERATE_MAX_B) return fail(PSCL_EUNSUP, "B exceeds the %lld rows of one launch", PSCL_DERATE_MAX_B);
+    if (B == 0) return PSCL_OK;
+    const int rc = enter(h);
+    if (rc) return rc;
+    return launch_derate(h, d_llr, B, d_out, 0, h->stream, false, nullptr);
+}
+
+int pscl_set_rate_match_staged(pscl_handle* h, int enable) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if ((enable != 0) == h->rm_staged) return PSCL_OK;
+    const int rc = enter(h);  // (pending pipelined work first, as pscl_set_rate_match)
+    if (rc) return rc;
+    h->rm_staged = enable != 0;
+    return PSCL_OK;
+}
+
+int pscl_rm_staged_stats(pscl_handle* h, int64_t* passes, int64_t* rows, int reset) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (passes) *passes = h->n_rm_passes;
+    if (rows) *rows = h->n_rm_rows;
+    if (reset) h->n_rm_passes = h->n_rm_rows = 0;
     return PSCL_OK;
 }
 

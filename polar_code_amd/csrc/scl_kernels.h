@@ -296,6 +296,19 @@ struct pscl_encode_params {
 #define PSCL_ENCODE_MAX_B (4LL * 0x7fffffffLL)
 hipError_t pscl_launch_encode(const pscl_encode_params& P, hipStream_t s);
 
+// NR de-rate-matching as a pass of its own (derate.hip; pscl_derate_match_device and the staged mode,
+// pscl_set_rate_match_staged): out[b][i] = nr_stage(llr + b E, rm_src[i], E, N), the rows a plain-row
+// kernel then decodes.  A block of its own, as pscl_encode_params: no existing block grows.
+struct pscl_derate_params {
+    const double* llr;           // [B][E] received LLRs (8-byte aligned rows)
+    double* out;                 // [B][N]
+    int64_t B;
+    int n, E;                    // N = 1 << n (1..10); E > 0
+};
+// frames of one launch: its grid covers the batch in one pass (one workgroup per frame at N = 1024)
+#define PSCL_DERATE_MAX_B 0x7fffffffLL
+hipError_t pscl_launch_derate(const pscl_derate_params& P, hipStream_t s);
+
 // Lane-parallel successive cancellation of the N = 128 codes (sc128_lane.hip): stage 1 of
 // pscl_adaptive_device.  Frame b's hard-decision SC result (polar.py:130-168) goes to best / flags
 // (PSCL_FLAG_CRC_PASS | 0 when check_crc holds, else 0) and stage (1 pass, 2 fail).

@@ -395,6 +395,30 @@ class SCLDecoder:
                 code = code.reshape(B, dec.code_words)
         return {"msg": _unpack_words(msg, self.K), "code": _unpack_words(code, E)}
 
+    def derate_match_tensor(self, llr):
+        """The NR front end alone on the caller's current torch stream, without a host wait
+        (pscl_derate_match_device; native.set_rate_match(E) first): llr, a contiguous float64 [B, E]
+        tensor of received LLRs on this decoder's GPU -> the [B, N] float64 decoder-internal rows,
+        subblock_deinterleave(derate_match_polar(row, N), N) bit for bit.  A plain decoder of the same
+        code decodes them to this decoder's results on llr."""
+        import torch
+
+        if self.device == "cpu":
+            raise ValueError("the tensor methods need a GPU decoder")
+        E = self._dec.E
+        if not E:
+            raise ValueError("the decoder has no rate matching (native.set_rate_match)")
+        if (not isinstance(llr, torch.Tensor) or llr.dtype != torch.float64 or not llr.is_contiguous() or llr.dim() != 2
+                or llr.shape[1] != E):
+            raise ValueError(f"llr must be a contiguous float64 [B, {E}] tensor")
+        if llr.device.type != "cuda" or llr.device.index != self.device:
+            raise ValueError(f"llr must be on GPU {self.device}")
+        B = llr.shape[0]
+        out = torch.empty((B, self.N), dtype=torch.float64, device=llr.device)
+        self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
+        self._dec.derate_match_device(llr.data_ptr(), B, out.data_ptr())
+        return out
+
     def _payload_tensor(self, payload_words):
         """Validate payload_words for the tensor methods -- a contiguous int64 [B, payload_words]
         tensor on this decoder's GPU; anything else raises ValueError before any device call."""
