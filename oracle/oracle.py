@@ -13,33 +13,44 @@ import numpy as np
 
 _HERE = Path(__file__).resolve().parent
 _LIB = None
+_LIB_F32TAIL = None
 
 
-def lib() -> C.CDLL:
-    global _LIB
+def lib(f32tail: bool = False) -> C.CDLL:
+    """The oracle.  f32tail: liboracle_scl_f32tail.so instead, the same source built with
+    -DORACLE_TAIL_F32 -- the model of a screening decoder without its margin (decode_batch_f32tail)."""
+    global _LIB, _LIB_F32TAIL
+    if f32tail:
+        if _LIB_F32TAIL is None:
+            _LIB_F32TAIL = _load("liboracle_scl_f32tail.so")
+        return _LIB_F32TAIL
     if _LIB is None:
-        path = _HERE / "liboracle_scl.so"
-        if not path.exists():
-            raise RuntimeError(f"{path} missing: run python -m polar_code_amd.build")
-        L = C.CDLL(str(path))
-        dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
-        L.oracle_attach_crc.argtypes = [bp, C.c_int, C.c_uint64, bp]
-        L.oracle_check_crc.argtypes = [bp, C.c_int, C.c_uint64]
-        L.oracle_polar_transform.argtypes = [bp, C.c_int]
-        L.oracle_construct_info_set.argtypes = [C.c_int, C.c_int, C.c_double, ip]
-        L.oracle_sc_decode.argtypes = [dp, C.c_int, ip, C.c_int, bp]
-        L.oracle_decode_scl.argtypes = [dp, C.c_int, ip, C.c_int, C.c_int, C.c_uint64, bp, bp, dp, dp, ip]
-        L.oracle_decode_with_retries.argtypes = [dp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_uint64,
-                                                 C.POINTER(C.c_float), bp, ip, ip, ip, ip]
-        L.oracle_decode_batch.argtypes = [dp, C.c_int64, C.c_int, ip, C.c_int, C.c_int, C.c_uint64, bp,
-                                          C.POINTER(C.c_uint8), ip]
-        L.oracle_dl_batch.argtypes = [dp, C.c_int64, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_uint64,
-                                      C.POINTER(C.c_float), bp, ip, ip]
-        L.oracle_num_threads.restype = C.c_int
-        L.oracle_set_num_threads.argtypes = [C.c_int]
-        L.oracle_logaddexp0_batch.argtypes = [dp, C.c_int64, dp]
-        _LIB = L
+        _LIB = _load("liboracle_scl.so")
     return _LIB
+
+
+def _load(name: str) -> C.CDLL:
+    path = _HERE / name
+    if not path.exists():
+        raise RuntimeError(f"{path} missing: run python -m polar_code_amd.build")
+    L = C.CDLL(str(path))
+    dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int8)
+    L.oracle_attach_crc.argtypes = [bp, C.c_int, C.c_uint64, bp]
+    L.oracle_check_crc.argtypes = [bp, C.c_int, C.c_uint64]
+    L.oracle_polar_transform.argtypes = [bp, C.c_int]
+    L.oracle_construct_info_set.argtypes = [C.c_int, C.c_int, C.c_double, ip]
+    L.oracle_sc_decode.argtypes = [dp, C.c_int, ip, C.c_int, bp]
+    L.oracle_decode_scl.argtypes = [dp, C.c_int, ip, C.c_int, C.c_int, C.c_uint64, bp, bp, dp, dp, ip]
+    L.oracle_decode_with_retries.argtypes = [dp, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_uint64,
+                                             C.POINTER(C.c_float), bp, ip, ip, ip, ip]
+    L.oracle_decode_batch.argtypes = [dp, C.c_int64, C.c_int, ip, C.c_int, C.c_int, C.c_uint64, bp,
+                                      C.POINTER(C.c_uint8), ip]
+    L.oracle_dl_batch.argtypes = [dp, C.c_int64, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_uint64,
+                                  C.POINTER(C.c_float), bp, ip, ip]
+    L.oracle_num_threads.restype = C.c_int
+    L.oracle_set_num_threads.argtypes = [C.c_int]
+    L.oracle_logaddexp0_batch.argtypes = [dp, C.c_int64, dp]
+    return L
 
 
 def _p(a, t):
@@ -129,9 +140,10 @@ def decode_with_retries(llr, info, M, retries, crc=None, beta=None):
     return dict(bits=bits, success=bool(succ[0]), attempts=int(att[0]), tried=tried[: nt[0]].tolist())
 
 
-def decode_batch(llr, info, M, crc=None, want_idx=False):
+def decode_batch(llr, info, M, crc=None, want_idx=False, f32tail=False):
     """Parallel (OpenMP) batch decode: returns (best_bits[B,K], crc_pass[B]) and, with
-    want_idx, best_index[B] (the best candidate's list position) as a third element."""
+    want_idx, best_index[B] (the best candidate's list position) as a third element.
+    f32tail: the un-margined model's results (decode_batch_f32tail), never an expected value."""
     llr = np.ascontiguousarray(llr, np.float64)
     info = np.ascontiguousarray(info, np.int32)
     B, N = llr.shape
@@ -139,10 +151,18 @@ def decode_batch(llr, info, M, crc=None, want_idx=False):
     bits = np.zeros((B, K), np.int8)
     ok = np.zeros(B, np.uint8)
     idx = np.zeros(B, np.int32) if want_idx else None
-    if lib().oracle_decode_batch(_p(llr, C.c_double), B, N, _p(info, C.c_int32), K, M, poly_int(crc),
-                                 _p(bits, C.c_int8), _p(ok, C.c_uint8), None if idx is None else _p(idx, C.c_int32)):
+    if lib(f32tail).oracle_decode_batch(_p(llr, C.c_double), B, N, _p(info, C.c_int32), K, M, poly_int(crc),
+                                        _p(bits, C.c_int8), _p(ok, C.c_uint8),
+                                        None if idx is None else _p(idx, C.c_int32)):
         raise ValueError("oracle_decode_batch failed")
     return (bits, ok.astype(bool), idx) if want_idx else (bits, ok.astype(bool))
+
+
+def decode_batch_f32tail(llr, info, M, crc=None, want_idx=False):
+    """decode_batch of the model whose metric tail is the screening kernels' fp32 approximation and
+    which defers nothing (scl_oracle.c ORACLE_TAIL_F32).  The near-tie tests count the frames on which
+    it differs from decode_batch: rows on which a decoder that ignored its margin would be wrong."""
+    return decode_batch(llr, info, M, crc=crc, want_idx=want_idx, f32tail=True)
 
 
 def dl_batch(llr, info, M, retries, crc=None, beta=None):

@@ -186,12 +186,26 @@ int oracle_sc_decode(const double* llr, int N, const int32_t* info, int K, int8_
 
 /* np.logaddexp(0.0, v) via npy_logaddexp with libm exp/log1p. */
 static inline double logaddexp0(double v) {
+#ifdef ORACLE_TAIL_F32
+    /*
+     * TESTS ONLY (oracle/liboracle_scl_f32tail.so; tests/near_tie_cases.py): the model of a
+     * screening decoder WITHOUT its ordering margin.  logaddexp(0, v) = max(v, 0) + log1p(exp(-|v|));
+     * only the tail is swapped, for the host form of csrc/glibc_softplus.h pscl_softplus_tail_abs
+     * (fp32 exp2 / log2 of fl32(|v|), about 1.4e-7 absolute error per increment).  Nothing is
+     * deferred, so this build is wrong wherever two metrics lie closer than that error: it is what
+     * the near-tie fixture is measured against, never an expected value.
+     */
+    const float x32 = (float)fabs(v);
+    const double tail = (double)(log2f(1.0f + exp2f(x32 * -1.44269504088896341f)) * 0.693147180559945309f);
+    return (v > 0.0 ? v : 0.0) + tail;
+#else
     const double x = 0.0, y = v;
     if (x == y) return x + 0.693147180559945309417232121458176568;
     double tmp = x - y;
     if (tmp > 0) return x + log1p(exp(-tmp));
     if (tmp <= 0) return y + log1p(exp(tmp));
     return tmp;
+#endif
 }
 
 typedef struct {

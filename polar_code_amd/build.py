@@ -2,6 +2,7 @@
 
   polar_code_amd/libpolar_mi355x.so   HIP kernels + C ABI for gfx950 (the product)
   oracle/liboracle_scl.so             C restatement of the reference (test/baseline only)
+  oracle/liboracle_scl_f32tail.so     the same source with -DORACLE_TAIL_F32 (near-tie fixture only)
   oracle/libsoftplus_host.so          host build of csrc/glibc_softplus.h (parity test only)
 
 Run:  python -m polar_code_amd.build   (or __graft_entry__.build()).
@@ -169,6 +170,12 @@ def build_oracle(force: bool = False) -> list[Path]:
         _run(["gcc", "-O2", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-fno-builtin",
               str(src), "-o", str(lib), "-lm"])
     out.append(lib)
+    # the same source with the metric tail of an un-margined screening decoder (tests/near_tie_cases.py)
+    f32 = ORACLE / "liboracle_scl_f32tail.so"
+    if force or _stale(f32, [src]):
+        _run(["gcc", "-O2", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-fno-builtin", "-DORACLE_TAIL_F32",
+              str(src), "-o", str(f32), "-lm"])
+    out.append(f32)
     sp = ORACLE / "libsoftplus_host.so"
     spsrc = ORACLE / "softplus_host.c"
     if force or _stale(sp, [spsrc, CSRC / "glibc_softplus.h", CSRC / "exp_table.inc"]):
