@@ -59,7 +59,8 @@ extern "C" {
 
 #define PSCL_MAX_N 1024  /* code length N: power of two, 2..1024 (N <= 128: the specialised kernels,
                             every BASELINE config; 256..1024: one wavefront per frame, global scratch;
-                            the decision-LLR replay pscl_path_llrs_device stops at 128) */
+                            the decision-LLR replay pscl_path_llrs_device takes every N on float64
+                            rows, its float32 form pscl_path_llrs_device_f32 N = 128 only) */
 #define PSCL_MAX_L 32    /* list size M/L: 1..32 (2L candidates fit one 64-lane wavefront) */
 #define PSCL_MAX_CRC 32  /* CRC degree: 1..32 */
 #define PSCL_WORDS(K) (((K) + 63) / 64)
@@ -274,8 +275,18 @@ int pscl_rm_staged_stats(pscl_handle* h, int64_t* passes, int64_t* rows, int res
  * information phase, recomputed top-down through the same f/g operations as the decoder
  * (bit-identical to the decoder's info_llrs for that path).  Device buffers, handle stream.
  *   d_llr [B][N] (or [B][E] with rate matching);  d_bits [B][W] uint64;  d_out [B][K] float64
+ * Every N the handle takes: N <= 128 on the replay kernel of the DL-SCL post pass, N = 256, 512,
+ * 1024 on the long replay kernel (one wavefront per row, the tree level in registers), plain and
+ * rate-matched rows alike.  B <= 2^31 - 1; B = 0 returns at once.  The call synchronizes the
+ * handle's stream once.  (float32 rows: pscl_path_llrs_device_f32, N = 128 only.)
+ *
+ * pscl_replay_stats: launches of the long replay kernel and the rows they were sized for since the
+ * handle was created (or the last reset = 1), from pscl_path_llrs_device and from the DL-SCL chains
+ * under PSCL_TUNE_DL_LONG_REPLAY -- there the only sign that the replay route ran.  Launches at
+ * N <= 128 are not counted.  Either pointer may be NULL.
  */
 int pscl_path_llrs_device(pscl_handle* h, const double* d_llr, int64_t B, const uint64_t* d_bits, double* d_out);
+int pscl_replay_stats(pscl_handle* h, int64_t* launches, int64_t* rows, int reset);
 
 /*
  * DL-SCL flip metric matrix (dl_scl_polar/dlscl/flip.py:104-106, checkpoints/beta_M*.npy):
@@ -686,6 +697,12 @@ int pscl_join(pscl_handle* h);
  *                           (its workgroups then stride over the list); 0 (default): a grid sized
  *                           for B, whose workgroups past the count exit at once -- the measured
  *                           faster
+ *   PSCL_TUNE_DL_LONG_REPLAY 1: the long codes' DL-SCL chain (N = 256..1024: pscl_dlscl_device,
+ *                           pscl_retry_device, pscl_adaptive_dlscl_device, pscl_simulate*, pipelined
+ *                           handles) takes every attempt's L0 from the decision-LLR replay: no second
+ *                           baseline decode, and retry decodes without history; 0 (default): the
+ *                           decodes with history.  Every output and counter is bit-identical either
+ *                           way (pscl_replay_stats tells them apart); no effect at N <= 128
  */
 #define PSCL_TUNE_DL_SCREEN 1
 #define PSCL_TUNE_DL_CHUNKS 2
@@ -705,7 +722,8 @@ int pscl_join(pscl_handle* h);
 #define PSCL_TUNE_DL_WARM_APX 16
 #define PSCL_TUNE_DL_TAIL 17
 #define PSCL_TUNE_ADAPT_GRID 18
-#define PSCL_TUNE_COUNT 19
+#define PSCL_TUNE_DL_LONG_REPLAY 19
+#define PSCL_TUNE_COUNT 20
 int pscl_set_tuning(pscl_handle* h, int knob, int64_t value);
 
 /*
@@ -775,6 +793,16 @@ int pscl_path_stats(pscl_handle* h, int64_t* fused_post_rounds, int64_t* post_ro
 int pscl_decode_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly, const double* llr, int64_t B,
                     const int8_t* forced, int32_t* n_paths, int8_t* best_bits, uint8_t* crc_pass, int32_t* best_idx,
                     double* metrics, int8_t* cands, double* info_llrs, int threads);
+
+/*
+ * pscl_path_llrs_device on the host, without a GPU or a handle: the decision LLRs out [B][K] of the
+ * paths with information bits `bits` [B][K] (int8 0/1; frozen bits 0) on the decoder-internal rows
+ * llr [B][N] (the de-rate-matched ones), bit-identical to pscl_decode_cpu's info_llrs of the
+ * candidate with those bits.  Any power-of-two N <= PSCL_MAX_N; conventions as pscl_decode_cpu.
+ * PSCL_EINVAL for invalid arguments; B = 0 is PSCL_OK.  No HIP call is made.
+ */
+int pscl_path_llrs_cpu(int N, const int32_t* info_set, int K, const double* llr, int64_t B, const int8_t* bits,
+                       double* out, int threads);
 
 /*
  * pscl_adaptive_device's contract on the host, without a GPU or a handle: sc_decode

@@ -25,7 +25,7 @@ PSCL_ENOMEM = -3
 PSCL_EPRUNED = -4
 PSCL_EUNSUP = -5
 PSCL_MAX_N = 1024
-PSCL_REPLAY_MAX_N = 128  # pscl_path_llrs_device (decision-LLR replay); TX, decode and the DL-SCL loop take any N
+PSCL_REPLAY_MAX_N = 1024  # pscl_path_llrs_device (decision-LLR replay) on float64 rows; the float32 form takes N = 128 only
 PSCL_MAX_L = 32
 PSCL_FLAG_CRC_PASS = 0x80
 PSCL_FLAG_IDX_MASK = 0x3F
@@ -52,11 +52,12 @@ EXPORTS = (
     "pscl_dlscl_device_f32", "pscl_retry_device_f32", "pscl_adaptive_dlscl_device_f32", "pscl_path_llrs_device_f32",
     "pscl_encode_device", "pscl_channel_payload_device", "pscl_encode_cpu",
     "pscl_derate_match_device", "pscl_set_rate_match_staged", "pscl_rm_staged_stats",
+    "pscl_path_llrs_cpu", "pscl_replay_stats",
 )
 
 # pscl_set_tuning knobs (include/polar_scl.h)
 TUNE = {"dl_screen": 1, "dl_chunks": 2, "dl_split": 3, "side_priority": 4, "post_grid": 5, "retry_wpg": 6, "dl_lane": 7, "dl_screen_min": 8, "dl_retry_lane": 9, "post_pairs": 10, "dl_streams": 11, "tx_fused": 12,
-        "dl_fused_post": 13, "post_epw": 14, "lane_exact": 15, "dl_warm_apx": 16, "dl_tail": 17, "adapt_grid": 18}
+        "dl_fused_post": 13, "post_epw": 14, "lane_exact": 15, "dl_warm_apx": 16, "dl_tail": 17, "adapt_grid": 18, "dl_long_replay": 19}
 
 _vp, _i32, _i64, _u64, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
 
@@ -177,6 +178,8 @@ def lib() -> C.CDLL:
         "pscl_derate_match_device": (C.c_int, [_vp, _vp, _i64, _vp]),
         "pscl_set_rate_match_staged": (C.c_int, [_vp, C.c_int]),
         "pscl_rm_staged_stats": (C.c_int, [_vp, P(_i64), P(_i64), C.c_int]),
+        "pscl_replay_stats": (C.c_int, [_vp, P(_i64), P(_i64), C.c_int]),
+        "pscl_path_llrs_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, _vp, _i64, _vp, _vp, C.c_int]),
         "pscl_set_beta": (C.c_int, [_vp, _vp]),
         "pscl_path_llrs_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
         "pscl_uncoded_device": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, C.c_int, _i64, _i64, _vp]),
@@ -279,6 +282,13 @@ class Decoder:
         a, b = _i64(), _i64()
         check(lib().pscl_rm_staged_stats(self._h, C.byref(a), C.byref(b), 1 if reset else 0))
         return {"passes": int(a.value), "rows": int(b.value)}
+
+    def replay_stats(self, reset: bool = False) -> dict:
+        """Launches of the long replay kernel (N = 256..1024) and the rows they were sized for
+        (pscl_replay_stats): pscl_path_llrs_device's and the DL-SCL chains' under dl_long_replay."""
+        a, b = _i64(), _i64()
+        check(lib().pscl_replay_stats(self._h, C.byref(a), C.byref(b), 1 if reset else 0))
+        return {"launches": int(a.value), "rows": int(b.value)}
 
     @property
     def _h(self):
@@ -902,6 +912,22 @@ class CpuDecoder:
                                              self.threads))
         return {"best_bits": bits, "crc_pass": ok.astype(bool), "best_idx": idx, "stage": stage,
                 "n_escalated": int(np.count_nonzero(stage == 2))}
+
+    def path_llrs(self, llr: np.ndarray, bits: np.ndarray) -> np.ndarray:
+        """Decoder.path_llrs on the host (pscl_path_llrs_cpu): llr [B, N], bits [B, K] 0/1 ->
+        decision LLRs [B, K] of the paths with those information bits."""
+        llr = np.ascontiguousarray(llr, dtype=np.float64)
+        if llr.ndim == 1:
+            llr = llr[None, :]
+        B = llr.shape[0]
+        if llr.shape[1] != self.N:
+            raise ValueError("Channel LLR length must be a power of two")
+        bits = np.ascontiguousarray(np.asarray(bits).reshape(B, self.K), dtype=np.int8)
+        out = np.zeros((B, self.K), np.float64)
+        if B:
+            check(lib().pscl_path_llrs_cpu(self.N, self.info_set.ctypes.data_as(C.POINTER(_i32)), self.K, _ptr(llr), B,
+                                           _ptr(bits), _ptr(out), self.threads))
+        return out
 
     def sync(self) -> None:
         pass

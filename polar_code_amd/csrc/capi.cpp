@@ -217,6 +217,7 @@ struct pscl_handle {
     // an adaptive call of parity q, which its stage 2 reads on a side stream
     bool rm_staged = false;
     int64_t n_rm_passes = 0, n_rm_rows = 0;  // pscl_rm_staged_stats
+    int64_t n_replay_launches = 0, n_replay_rows = 0;  // pscl_replay_stats (the long replay kernel)
 };
 
 namespace {
@@ -1436,7 +1437,7 @@ int pscl_set_tuning(pscl_handle* h, int knob, int64_t value) {
     if (!h) return fail(PSCL_EINVAL, "NULL handle");
     static const int64_t lim[PSCL_TUNE_COUNT][2] = {{0, 0}, {0, 2}, {0, 64}, {0, 2}, {0, 1}, {0, 4096}, {0, PSCL_MAX_WAVES_PER_WG}, {0, 2},
                                                     {0, (int64_t)1 << 30}, {0, 2}, {0, 32}, {0, 3}, {0, 2}, {0, 2}, {0, 4}, {0, 3}, {0, 2}, {0, 1},
-                                                    {0, (int64_t)1 << 20}};
+                                                    {0, (int64_t)1 << 20}, {0, 1}};
     if (knob < 1 || knob >= PSCL_TUNE_COUNT) return fail(PSCL_EINVAL, "unknown tuning knob %d", knob);
     if (value < lim[knob][0] || value > lim[knob][1] || (knob == PSCL_TUNE_POST_GRID && value && value < 16))
         return fail(PSCL_EINVAL, "tuning knob %d: value %lld out of range", knob, (long long)value);
@@ -1457,7 +1458,6 @@ int path_llrs_impl(pscl_handle* h, const void* d_llr, bool f32, int64_t B, const
     if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
     if (B == 0) return PSCL_OK;
     if (!d_llr || !d_bits || !d_out) return fail(PSCL_EINVAL, "d_llr, d_bits and d_out are required");
-    if (h->N > PSCL_FAST_N) return fail(PSCL_EUNSUP, "decision-LLR replay supports N <= %d", PSCL_FAST_N);
     if (f32 && h->N != PSCL_FAST_N)
         return fail(PSCL_EUNSUP, "float32 rows: the decision-LLR replay takes N = %d only (N = %d)", PSCL_FAST_N, h->N);
     if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
@@ -1487,8 +1487,14 @@ int path_llrs_impl(pscl_handle* h, const void* d_llr, bool f32, int64_t B, const
     Rp.bits = d_bits;
     Rp.bits_by_row = 1;
     Rp.out = d_out;
-    if ((e = pscl_launch_replay(Rp, B, h->stream)) != hipSuccess)
-        return fail(PSCL_EDEVICE, "replay launch: %s", hipGetErrorString(e));
+    if (h->N > PSCL_FAST_N) {  // the long replay kernel (replay_long.hip): the mask by words, on the device
+        e = pscl_launch_replay_long(Rp, B, h->d_info_words, nullptr, h->stream);
+        h->n_replay_launches++;
+        h->n_replay_rows += B;
+    } else {
+        e = pscl_launch_replay(Rp, B, h->stream);
+    }
+    if (e != hipSuccess) return fail(PSCL_EDEVICE, "replay launch: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(h->stream));  // d_cnt is a host-staged value
     return PSCL_OK;
 }
@@ -1807,16 +1813,46 @@ int dl_retry_long(pscl_handle* h, const DlLongState& S, int64_t* act0, const int
     hipError_t e;
     int rc;
     HIP_TRY(hipMemsetAsync(S.cnt, 0, (size_t)(rounds + 2) * 4, st));
+    // PSCL_TUNE_DL_LONG_REPLAY: every attempt's L0 from the long replay kernel (replay_long.hip) -- the
+    // baseline's over (act0, d_best by frame), which also copies those bits to S.ob for the first post
+    // pass, with no second baseline decode; a round's over (its entries, S.ob by entry) after a retry
+    // decode without history.  The same values bit for bit (the replay's contract)
+    const bool rpl = h->tune[PSCL_TUNE_DL_LONG_REPLAY] == 1;
+    const int hist = rpl ? 0 : 1;
+    pscl_replay_params Rp;
+    memset(&Rp, 0, sizeof(Rp));
+    Rp.llr = d_llr;
+    Rp.N = h->N;
+    Rp.n = h->n;
+    Rp.K = h->K;
+    Rp.W = h->W;
+    Rp.rm_E = h->rm_E;
+    Rp.rm_src = h->d_rm_src;
+    Rp.out = S.l0;
+    auto replay = [&](const int32_t* count, const int64_t* act, const uint64_t* bits, int by_row, uint64_t* ob_copy) {
+        Rp.count = count;
+        Rp.act = act;
+        Rp.bits = bits;
+        Rp.bits_by_row = by_row;
+        h->n_replay_launches++;
+        h->n_replay_rows += A;
+        return pscl_launch_replay_long(Rp, A, h->d_info_words, ob_copy, st);
+    };
     pscl_decode_params H;
-    fill_decode_params(h, H, 1);
+    fill_decode_params(h, H, hist);
     H.llr = d_llr;
     H.B = A;
     H.fidx = act0;
     H.d_count = cnt0;
     H.best = S.ob;
     H.flags = S.of;
-    H.best_info_llrs = S.l0;
-    if ((rc = launch_decode(h, H, 1, st, kLongRetryScratch))) return rc;
+    H.best_info_llrs = rpl ? nullptr : S.l0;
+    if (rpl) {
+        if ((e = replay(cnt0, act0, d_best, 1, S.ob)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "replay launch: %s", hipGetErrorString(e));
+    } else if ((rc = launch_decode(h, H, 1, st, kLongRetryScratch))) {
+        return rc;
+    }
     pscl_post_long_params Q;
     memset(&Q, 0, sizeof(Q));
     Q.K = h->K;
@@ -1850,7 +1886,9 @@ int dl_retry_long(pscl_handle* h, const DlLongState& S, int64_t* act0, const int
         H.fidx = acts[c];
         H.d_count = S.cnt + r + 1;
         H.force = S.force;
-        if ((rc = launch_decode(h, H, 1, st, kLongRetryScratch))) return rc;
+        if ((rc = launch_decode(h, H, hist, st, kLongRetryScratch))) return rc;
+        if (rpl && (e = replay(S.cnt + r + 1, acts[c], S.ob, 0, nullptr)) != hipSuccess)
+            return fail(PSCL_EDEVICE, "replay launch: %s", hipGetErrorString(e));
         Q.in_count = S.cnt + r + 1;
         Q.out_count = S.cnt + r + 2;
         Q.act_in = acts[c];
@@ -2961,6 +2999,14 @@ int pscl_rm_staged_stats(pscl_handle* h, int64_t* passes, int64_t* rows, int res
     if (passes) *passes = h->n_rm_passes;
     if (rows) *rows = h->n_rm_rows;
     if (reset) h->n_rm_passes = h->n_rm_rows = 0;
+    return PSCL_OK;
+}
+
+int pscl_replay_stats(pscl_handle* h, int64_t* launches, int64_t* rows, int reset) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (launches) *launches = h->n_replay_launches;
+    if (rows) *rows = h->n_replay_rows;
+    if (reset) h->n_replay_launches = h->n_replay_rows = 0;
     return PSCL_OK;
 }
 

@@ -199,7 +199,59 @@ void sc_segment(const double* seg, int w, int start, const uint8_t* is_info, dou
     for (int i = 0; i < h; ++i) x[i] ^= x[i + h];
 }
 
+// sc_segment with the path's bits given (ubits[phase], frozen phases 0) instead of decided: the
+// leaf LLR of every phase goes to leaf[].  The decoder's lazy tree computes the same f/g of the same
+// operands for the path with these bits, so leaf[info phase] is its decision LLR (scl.py:158,166)
+void replay_segment(const double* seg, int w, int start, const uint8_t* ubits, double* work, double* leaf, uint8_t* x) {
+    if (w == 1) {
+        leaf[start] = seg[0];
+        x[0] = ubits[start];
+        return;
+    }
+    const int h = w / 2;
+    for (int i = 0; i < h; ++i) work[i] = f_node(seg[i], seg[i + h]);
+    replay_segment(work, h, start, ubits, work + h, leaf, x);
+    for (int i = 0; i < h; ++i) work[i] = g_node(seg[i], seg[i + h], x[i]);
+    replay_segment(work, h, start + h, ubits, work + h, leaf, x + h);
+    for (int i = 0; i < h; ++i) x[i] ^= x[i + h];
+}
+
 }  // namespace
+
+// pscl_path_llrs_device on the host: the decision LLRs of the paths with the given information bits
+extern "C" int pscl_path_llrs_cpu(int N, const int32_t* info_set, int K, const double* llr, int64_t B, const int8_t* bits,
+                                  double* out, int threads) {
+    if (N < 2 || N > PSCL_MAX_N || (N & (N - 1))) return PSCL_EINVAL;
+    if (K < 0 || K > N || B < 0 || (K && !info_set)) return PSCL_EINVAL;
+    for (int i = 0; i < K; ++i)
+        if (info_set[i] < 0 || info_set[i] >= N || (i && info_set[i] <= info_set[i - 1])) return PSCL_EINVAL;
+    if (B == 0) return PSCL_OK;
+    if (!llr || (K && (!bits || !out))) return PSCL_EINVAL;
+    for (int64_t i = 0; i < B * K; ++i)
+        if (bits[i] != 0 && bits[i] != 1) return PSCL_EINVAL;
+    int T = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    if (T < 1) T = 1;
+    if ((int64_t)T > B) T = (int)B;
+    auto work = [&](int t) {
+        std::vector<double> tmp((size_t)N), leaf((size_t)N);
+        std::vector<uint8_t> u((size_t)N), x((size_t)N);
+        const int64_t b0 = B * t / T, b1 = B * (t + 1) / T;
+        for (int64_t b = b0; b < b1; ++b) {
+            std::fill(u.begin(), u.end(), (uint8_t)0);
+            for (int i = 0; i < K; ++i) u[(size_t)info_set[i]] = (uint8_t)bits[b * K + i];
+            replay_segment(llr + b * N, N, 0, u.data(), tmp.data(), leaf.data(), x.data());
+            for (int i = 0; i < K; ++i) out[b * K + i] = leaf[(size_t)info_set[i]];
+        }
+    };
+    if (T == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < T; ++t) pool.emplace_back(work, t);
+        for (auto& th : pool) th.join();
+    }
+    return PSCL_OK;
+}
 
 // SC first, the list decoder where its result fails the CRC (pscl_adaptive_device's contract)
 extern "C" int pscl_decode_adaptive_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly,

@@ -471,6 +471,11 @@ hipError_t pscl_launch_replay(const pscl_replay_params& R, int64_t cap, hipStrea
 // the float32-row forms of the replay and the post pass (dlscl_f32.hip); pscl_launch_replay and
 // pscl_launch_dl_post hand a launch with R.row_f32 / Q.row_f32 set to them
 hipError_t pscl_launch_replay_f32(const pscl_replay_params& R, int64_t cap, hipStream_t s);
+// the replay of the long codes (replay_long.hip; N = 256, 512, 1024, float64 rows): info_words the
+// N / 64 words of the information mask (device), ob_copy null or [entries][W] -- each entry's bit
+// words copied there
+hipError_t pscl_launch_replay_long(const pscl_replay_params& R, int64_t cap, const uint64_t* info_words,
+                                   uint64_t* ob_copy, hipStream_t s);
 hipError_t pscl_launch_dl_post_f32(const pscl_post_params& Q, int64_t entries, hipStream_t s);
 hipError_t pscl_launch_tail_abs_scan(uint32_t lo, uint32_t hi, const uint64_t* exp_table, unsigned long long* out,
                                      hipStream_t s, int bits);

@@ -363,6 +363,36 @@ class SCLDecoder:
             self._dec.join()  # (the widened temporary: see decode_tensor)
         return best, flags, stage, attempts, tried, n_esc
 
+    def path_llrs_tensor(self, llr, best_words):
+        """Decision LLRs of known paths (pscl_path_llrs_device; scl.py:158,166) on the caller's current
+        torch stream: llr a contiguous float64 or float32 [B, N] (or [B, E]) tensor on this GPU,
+        best_words a contiguous int64 [B, W] tensor of the paths' information bits (decode_tensor's
+        best_words).  Returns a [B, K] float64 tensor, bit for bit the decoder's info_llrs of those
+        paths.  float64 rows at any N <= 1024; float32 rows natively at N = 128
+        (pscl_path_llrs_device_f32), elsewhere widened with llr.double() (see decode_tensor)."""
+        import torch
+
+        if self.device == "cpu":
+            raise ValueError("the tensor methods need a GPU decoder")
+        f32 = self._f32_rows(llr, self._dec.E or self.N)
+        B, W = llr.shape[0], self._dec.W
+        if (not isinstance(best_words, torch.Tensor) or best_words.dtype != torch.int64 or not best_words.is_contiguous()
+                or tuple(best_words.shape) != (B, W)):
+            raise ValueError(f"best_words must be a contiguous int64 [B, {W}] tensor")
+        if llr.device.type != "cuda" or llr.device.index != self.device or best_words.device != llr.device:
+            raise ValueError(f"llr and best_words must be on GPU {self.device}")
+        out = torch.empty((B, self.K), dtype=torch.float64, device=llr.device)
+        self._dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
+        if f32 and self.N == 128:
+            self._dec.path_llrs_device_f32(llr.data_ptr(), B, best_words.data_ptr(), out.data_ptr())
+            return out
+        if f32:
+            llr = llr.double()
+        self._dec.path_llrs_device(llr.data_ptr(), B, best_words.data_ptr(), out.data_ptr())
+        if f32:
+            self._dec.join()  # (the widened temporary: see decode_tensor)
+        return out
+
     # ---- caller payloads: payload -> CRC -> codeword (-> symbols or AWGN LLR rows) on the device
     def encode(self, payload_bits: np.ndarray, device=None) -> dict:
         """payload_bits [B, k_payload] 0/1 (k_payload = K - CRC degree) -> dict(msg [B, K] int8 =

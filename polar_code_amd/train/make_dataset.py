@@ -35,16 +35,18 @@ from ..polar.polar import construct_info_set, encode
 from ..utils.seeding import seed_all
 
 
-def decode_batch(llr: np.ndarray, info_set, M: int, crc, forced: Optional[np.ndarray] = None):
-    """(best bits [B, K] int8, CRC pass [B] bool) of decode_scl for a batch (GPU)."""
-    dec = _native.get_decoder(llr.shape[1], info_set, M, crc)
+def decode_batch(llr: np.ndarray, info_set, M: int, crc, forced: Optional[np.ndarray] = None, device=0):
+    """(best bits [B, K] int8, CRC pass [B] bool) of decode_scl for a batch (GPU `device`, or "cpu":
+    the host decoder)."""
+    dec = _native.get_decoder(llr.shape[1], info_set, M, crc, device)
     out = dec.decode(llr, forced, want_metrics=False, want_cands=False, want_info_llrs=False)
     return out["best_bits"], out["crc_pass"]
 
 
-def best_path_llrs(llr: np.ndarray, info_set, M: int, crc, bits: np.ndarray) -> np.ndarray:
-    """best_path_info_llrs [B, K] of the paths with information bits `bits` (GPU replay)."""
-    return _native.get_decoder(llr.shape[1], info_set, M, crc).path_llrs(llr, bits)
+def best_path_llrs(llr: np.ndarray, info_set, M: int, crc, bits: np.ndarray, device=0) -> np.ndarray:
+    """best_path_info_llrs [B, K] of the paths with information bits `bits`: the decision-LLR replay
+    of the decoder in use (GPU `device`, or "cpu": the host decoder's), any N the decoders take."""
+    return _native.get_decoder(llr.shape[1], info_set, M, crc, device).path_llrs(llr, bits)
 
 
 def _force_prefix_flip(bits: np.ndarray, idx: np.ndarray) -> np.ndarray:
@@ -57,15 +59,16 @@ def _force_prefix_flip(bits: np.ndarray, idx: np.ndarray) -> np.ndarray:
     return forced
 
 
-def label_batch(llr: np.ndarray, info_set, M: int, crc: str, sent: np.ndarray):
+def label_batch(llr: np.ndarray, info_set, M: int, crc: str, sent: np.ndarray, device=0):
     """Samples of one batch, in frame order: (abs_l0 float32 [S, K], labels int32 [S], failures)."""
-    bits, ok = decode_batch(llr, info_set, M, crc)
+    on = {} if device == 0 else {"device": device}  # (the default device: the helpers' own)
+    bits, ok = decode_batch(llr, info_set, M, crc, **on)
     fail = np.flatnonzero(~ok)
     K = bits.shape[1]
     if fail.size == 0:
         return np.zeros((0, K), np.float32), np.zeros(0, np.int32), 0
     base = bits[fail]
-    l0 = best_path_llrs(llr[fail], info_set, M, crc, base)
+    l0 = best_path_llrs(llr[fail], info_set, M, crc, base, **on)
     abs_l0 = np.abs(np.asarray(l0, dtype=np.float32))
     order = np.stack([np.argsort(row) for row in abs_l0])  # per frame, as make_dataset.py:71
     label = np.full(fail.size, -1, np.int32)
@@ -74,7 +77,7 @@ def label_batch(llr: np.ndarray, info_set, M: int, crc: str, sent: np.ndarray):
         if todo.size == 0:
             break
         idx = order[todo, t]
-        cand, cpass = decode_batch(llr[fail[todo]], info_set, M, crc, _force_prefix_flip(base[todo], idx))
+        cand, cpass = decode_batch(llr[fail[todo]], info_set, M, crc, _force_prefix_flip(base[todo], idx), **on)
         hit = cpass & np.all(cand == sent[None, :], axis=1)
         label[todo[hit]] = idx[hit]
     keep = label >= 0
@@ -120,7 +123,8 @@ def generate_samples(args: argparse.Namespace) -> Path:
             llr = 2.0 * (symbols[None, :] + noise) / noise_var
         else:
             llr = _philox_frames(args.seed, args.snr_db, b0, n, info_set, args.M, cfg.crc_poly, payload_bits)
-        a, lab, nf = label_batch(llr, info_set, args.M, cfg.crc_poly, sent)
+        dev = getattr(args, "device", "0")
+        a, lab, nf = label_batch(llr, info_set, args.M, cfg.crc_poly, sent, "cpu" if dev == "cpu" else int(dev))
         xs.append(a)
         ys.append(lab)
         failures += nf
@@ -151,6 +155,7 @@ def build_argparser() -> argparse.ArgumentParser:
     p.add_argument("--rng", choices=["replay", "philox"], default="replay",
                    help="replay: the reference's NumPy stream (identical samples); philox: GPU-generated frames")
     p.add_argument("--batch", type=int, default=1 << 16, help="frames per GPU batch")
+    p.add_argument("--device", type=str, default="0", help="GPU index, or cpu: the host decoder and its replay")
     return p
 
 
