@@ -22,6 +22,8 @@
  *   pscl_adaptive_device        <- sc_decode (polar.py:130-168) + check_crc (crc.py:40-56) on every
  *                                  frame of a device batch, decode_scl only where that fails
  *   pscl_path_llrs_device       <- best_path_info_llrs / info_llrs of given paths (scl.py:158,166)
+ *   pscl_label_device           <- the labelling loop of dl_scl_polar/train/make_dataset.py:52-91 over a
+ *                                  device batch: baseline, |L0| order, forced retries, labels
  *   pscl_simulate               <- one SNR point of run_sweep (run_fer_sweep.py:41-191): TX,
  *                                  uncoded baseline, SCL + DL-SCL, counters, in one call
  *
@@ -512,6 +514,57 @@ int pscl_adaptive_dlscl_device(pscl_handle* h, const double* d_llr, int64_t B, i
                                int32_t* d_n_escalated);
 
 /*
+ * Flip labels of a device batch: the labelling loop of dl_scl_polar/train/make_dataset.py:52-91 for
+ * every frame, with the frame's sent message in place of the reference's one all-zero-payload message.
+ * It is NOT decode_with_retries: the flip order is fixed once from the baseline, every attempt forces
+ * the BASELINE's prefix, and an attempt ends the chain only if it passes the CRC AND equals the sent
+ * message.  Per frame
+ *   1. the handle's plain list decode (pscl_decode_device's result).  A frame whose best candidate
+ *      passes the CRC produces nothing.
+ *   2. otherwise the frame is an ENTRY: abs_l0[k] = |(float)L0[k]|, L0 the decision LLRs of the
+ *      baseline best path (pscl_path_llrs_device's values, bit for bit), narrowed to float32 once
+ *      (round to nearest even) before the absolute value (make_dataset.py:66).
+ *   3. the T = min(max_flips, K) information indices of smallest abs_l0, ascending; EQUAL VALUES
+ *      RESOLVE TO THE LOWER INDEX.  (The rule is the engine's own: the reference's np.argsort is not
+ *      stable, so its order on ties depends on the NumPy build; without ties the two agree.)
+ *   4. for t = 0 .. T - 1: decode with the forced bits of flip.py:30-34 for idx_t -- the baseline bits
+ *      at the indices below idx_t, the complement at idx_t, the rest free.  The first t whose best
+ *      candidate passes the CRC and equals the frame's sent words gives flip = idx_t, rank = t, and
+ *      the entry's chain stops.  If no t qualifies, flip = rank = -1.
+ *   d_llr        [B][N] (or [B][E] with rate matching) float64
+ *   d_sent       the sent message words: [W] with sent_stride = 0 (one message for all frames, the
+ *                reference's case) or [B][W] with sent_stride = W (pscl_channel_device's d_msg)
+ *   max_flips    1 .. 32 (the reference: 8)
+ *   cap          entries the output arrays hold
+ *   d_frame      [cap] int64 out: the frame index of entry e
+ *   d_abs_l0     [cap][K] float32 out, for labelled and unrepaired entries alike
+ *   d_flip       [cap] int32 out: the label, or -1
+ *   d_rank       NULL or [cap] int32 out: its rank t, or -1
+ *   d_counts     int64[PSCL_NLABEL] out, written (not added): PSCL_LBL_*
+ *   n_entries    host out: A, the number of entries
+ * Entries e < A are written in unspecified order (the compaction's, not frame order); rows >= A are
+ * untouched.  The call makes one host wait, after the compaction, for A (pscl_dlscl_device's wait),
+ * and enqueues everything else on the handle's stream without a host trip: the replay of the
+ * baseline paths, the ranking, and per round the forced-bit decode of the live entries and the step
+ * that labels the hits and builds the next round's force words -- the rounds' lists and counts stay
+ * on the device.  If A > cap the call returns PSCL_EINVAL with *n_entries = A and no output written:
+ * the caller allocates again and repeats.  On a pipelined handle pending work is ordered first and
+ * the call runs stream-ordered, as pscl_retry_device.  Every N <= 1024, L and CRC pscl_dlscl_device
+ * takes, rate-matched handles included; float64 rows only.  No knob changes a result.
+ * PSCL_EINVAL without a CRC, for max_flips outside 1..32, B < 0, cap < 0, a sent_stride other than 0
+ * or W, and a NULL required pointer with B > 0; PSCL_EUNSUP for B > 2^31 - 1.  B = 0 returns PSCL_OK
+ * with zero counts and *n_entries = 0.
+ */
+#define PSCL_LBL_ENTRIES 0     /* frames whose baseline best candidate fails the CRC (A) */
+#define PSCL_LBL_LABELLED 1    /* entries with a label */
+#define PSCL_LBL_UNREPAIRED 2  /* entries without one (make_dataset's "failures") */
+#define PSCL_LBL_DECODES 3     /* forced decodes run, summed over the rounds */
+#define PSCL_NLABEL 4
+int pscl_label_device(pscl_handle* h, const double* d_llr, int64_t B, const uint64_t* d_sent, int64_t sent_stride,
+                      int max_flips, int64_t cap, int64_t* d_frame, float* d_abs_l0, int32_t* d_flip,
+                      int32_t* d_rank, int64_t* d_counts, int64_t* n_entries);
+
+/*
  * DL-SCL on float32 rows: the float32 contract above, carried on to the retry chains.  d_llr is
  * [B][N] (or [B][E]) float32, 4-byte aligned; the other arguments are those of the float64 forms.
  * Every output and every counter -- d_best, d_flags, d_stage, d_attempts, d_tried, d_n_escalated, each
@@ -803,6 +856,19 @@ int pscl_decode_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_p
  */
 int pscl_path_llrs_cpu(int N, const int32_t* info_set, int K, const double* llr, int64_t B, const int8_t* bits,
                        double* out, int threads);
+
+/*
+ * pscl_label_device's contract on the host, without a GPU or a handle, on pscl_decode_cpu's decoder
+ * and pscl_path_llrs_cpu's replay (same narrowing, same order, ties to the lower index).  llr [B][N]
+ * decoder-internal rows; sent int8 [K] (sent_stride = 0) or [B][K] (sent_stride = K).  Entries are in
+ * frame order and the arrays are sized for B entries: frame [B] int64, abs_l0 [B][K] float32, flip [B]
+ * int32, rank NULL or [B] int32 (rows at and above the entry count are untouched); counts
+ * int64[PSCL_NLABEL], written.  A CRC is required.  Argument errors as pscl_label_device's
+ * (PSCL_EINVAL); conventions as pscl_decode_cpu.  No HIP call is made.
+ */
+int pscl_label_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly, const double* llr, int64_t B,
+                   const int8_t* sent, int64_t sent_stride, int max_flips, int64_t* frame, float* abs_l0,
+                   int32_t* flip, int32_t* rank, int64_t* counts, int threads);
 
 /*
  * pscl_adaptive_device's contract on the host, without a GPU or a handle: sc_decode

@@ -53,7 +53,12 @@ EXPORTS = (
     "pscl_encode_device", "pscl_channel_payload_device", "pscl_encode_cpu",
     "pscl_derate_match_device", "pscl_set_rate_match_staged", "pscl_rm_staged_stats",
     "pscl_path_llrs_cpu", "pscl_replay_stats",
+    "pscl_label_device", "pscl_label_cpu",
 )
+
+# pscl_label_device / pscl_label_cpu counts (int64[PSCL_NLABEL])
+PSCL_NLABEL = 4
+LBL_ENTRIES, LBL_LABELLED, LBL_UNREPAIRED, LBL_DECODES = range(4)
 
 # pscl_set_tuning knobs (include/polar_scl.h)
 TUNE = {"dl_screen": 1, "dl_chunks": 2, "dl_split": 3, "side_priority": 4, "post_grid": 5, "retry_wpg": 6, "dl_lane": 7, "dl_screen_min": 8, "dl_retry_lane": 9, "post_pairs": 10, "dl_streams": 11, "tx_fused": 12,
@@ -180,6 +185,9 @@ def lib() -> C.CDLL:
         "pscl_rm_staged_stats": (C.c_int, [_vp, P(_i64), P(_i64), C.c_int]),
         "pscl_replay_stats": (C.c_int, [_vp, P(_i64), P(_i64), C.c_int]),
         "pscl_path_llrs_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, _vp, _i64, _vp, _vp, C.c_int]),
+        "pscl_label_device": (C.c_int, [_vp, _vp, _i64, _vp, _i64, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, P(_i64)]),
+        "pscl_label_cpu": (C.c_int, [C.c_int, P(_i32), C.c_int, C.c_int, _u64, _vp, _i64, _vp, _i64, C.c_int, _vp, _vp, _vp,
+                                     _vp, _vp, C.c_int]),
         "pscl_set_beta": (C.c_int, [_vp, _vp]),
         "pscl_path_llrs_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
         "pscl_uncoded_device": (C.c_int, [_vp, _u64, C.c_uint32, _dbl, C.c_int, _i64, _i64, _vp]),
@@ -228,6 +236,52 @@ def device_count() -> int:
 
 def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data
+
+
+class LabelCapacity(ValueError):
+    """pscl_label_device found more entries than the output arrays hold; `entries` is the count."""
+
+    def __init__(self, msg: str, entries: int):
+        super().__init__(msg)
+        self.entries = int(entries)
+
+
+def pack_bits(bits: np.ndarray, W: int) -> np.ndarray:
+    """[B, K] 0/1 -> [B, W] uint64 words, bit j at word j >> 6, bit j & 63 (include/polar_scl.h)."""
+    bits = np.asarray(bits)
+    B, K = bits.shape
+    pad = np.zeros((B, W * 64), np.uint8)
+    pad[:, :K] = bits
+    return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder="little")).view(np.uint64).reshape(B, W)
+
+
+def label_capacity(B: int, K: int) -> int:
+    """First capacity of a label call's output arrays: every frame while the |L0| rows stay under
+    256 MiB (no repeat is then possible), else a quarter of the batch, grown to the count the call
+    reports if that was short."""
+    B = int(B)
+    return max(B if B * K * 4 <= (1 << 28) else 1024 + B // 4, 1)
+
+
+def _sent_bits(sent, B: int, K: int) -> np.ndarray:
+    """The labeller's sent messages as int8 [1, K] (one for all frames) or [B, K]."""
+    s = np.asarray(sent)
+    if s.ndim == 1:
+        s = s[None, :]
+    elif s.ndim != 2 or s.shape[0] != B:
+        raise ValueError(f"sent must be [{K}] or [B, {K}]")
+    if s.shape[1] != K:
+        raise ValueError(f"sent must be [{K}] or [B, {K}]")
+    if np.any((s != 0) & (s != 1)):
+        raise ValueError("sent entries must be 0 or 1")
+    return np.ascontiguousarray(s, dtype=np.int8)
+
+
+def _sent_words(sent, B: int, K: int, W: int):
+    """(words, sent_stride) of pscl_label_device for sent [K] (stride 0) or [B, K] (stride W)."""
+    one = np.asarray(sent).ndim == 1
+    s = _sent_bits(sent, B, K)
+    return pack_bits(s, W), 0 if one else W
 
 
 def poly_value(crc) -> int:
@@ -603,6 +657,63 @@ class Decoder:
             self.path_llrs_device(d_llr, B, d_bits, d_out)
             return mem.download(d_out, B * self.K * 8, np.float64).reshape(B, self.K)
 
+    def label_device(self, d_llr: int, B: int, d_sent: int, sent_stride: int, max_flips: int, cap: int, *, d_frame: int,
+                     d_abs_l0: int, d_flip: int, d_rank=0, d_counts: int) -> int:
+        """Flip labels of B device-resident frames (pscl_label_device): baseline decode, |L0| order,
+        forced retries on the baseline's prefix, labels.  Returns A, the number of entries; raises
+        LabelCapacity (a ValueError carrying A) where A exceeds cap and nothing was written."""
+        n = _i64()
+        with self._lock:
+            rc = lib().pscl_label_device(self._h, d_llr or None, int(B), d_sent or None, int(sent_stride), int(max_flips),
+                                         int(cap), d_frame or None, d_abs_l0 or None, d_flip or None, d_rank or None,
+                                         d_counts or None, C.byref(n))
+        if rc == PSCL_EINVAL and n.value > int(cap):
+            raise LabelCapacity(last_error(), int(n.value))
+        check(rc)
+        return int(n.value)
+
+    def label(self, llr: np.ndarray, sent: np.ndarray, max_flips: int = 8, cap: int | None = None) -> dict:
+        """Host form of label_device: llr [B, N] (or [B, E]) float64, sent [K] or [B, K] 0/1 ->
+        dict(frame [A] int64, abs_l0 [A, K] float32, flip [A] int32, rank [A] int32, counts
+        int64[PSCL_NLABEL]), entries sorted by frame.  cap: the first capacity of the output arrays
+        (default label_capacity); the call is repeated once, with the count it reported, where that was short."""
+        llr = np.ascontiguousarray(llr, dtype=np.float64)
+        if llr.ndim == 1:
+            llr = llr[None, :]
+        B = llr.shape[0]
+        if llr.shape[1] != (self.E or self.N):
+            raise ValueError("Channel LLR length must be a power of two" if not self.E
+                             else f"expected {self.E} rate-matched LLRs per frame")
+        words, stride = _sent_words(sent, B, self.K, self.W)
+        K = self.K
+        with DeviceArena(self) as mem:
+            d_llr = mem.alloc(max(llr.nbytes, 8))
+            d_sent = mem.alloc(max(words.nbytes, 8))
+            d_counts = mem.alloc(PSCL_NLABEL * 8)
+            if B:
+                mem.upload(d_llr, llr)
+            mem.upload(d_sent, words)
+            cap = label_capacity(B, K) if cap is None else max(int(cap), 1)
+            for _ in range(2):
+                d_frame, d_abs = mem.alloc(cap * 8), mem.alloc(cap * K * 4)
+                d_flip, d_rank = mem.alloc(cap * 4), mem.alloc(cap * 4)
+                try:
+                    A = self.label_device(d_llr, B, d_sent, stride, max_flips, cap, d_frame=d_frame, d_abs_l0=d_abs,
+                                          d_flip=d_flip, d_rank=d_rank, d_counts=d_counts)
+                    break
+                except LabelCapacity as e:  # (allocate for the count the call reported, and repeat)
+                    if cap >= e.entries:
+                        raise
+                    cap = e.entries
+            self.sync()
+            counts = mem.download(d_counts, PSCL_NLABEL * 8, np.int64)
+            frame = mem.download(d_frame, cap * 8, np.int64)[:A]
+            abs_l0 = mem.download(d_abs, cap * K * 4, np.float32)[:A * K].reshape(A, K)
+            flip = mem.download(d_flip, cap * 4, np.int32)[:A]
+            rank = mem.download(d_rank, cap * 4, np.int32)[:A]
+        o = np.argsort(frame, kind="stable")
+        return {"frame": frame[o], "abs_l0": abs_l0[o], "flip": flip[o], "rank": rank[o], "counts": counts}
+
     def set_beta(self, beta: np.ndarray | None) -> None:
         """DL-SCL flip metric matrix [K, K] (None: rank by |L0|); widened to float64 exactly."""
         if beta is None:
@@ -928,6 +1039,29 @@ class CpuDecoder:
             check(lib().pscl_path_llrs_cpu(self.N, self.info_set.ctypes.data_as(C.POINTER(_i32)), self.K, _ptr(llr), B,
                                            _ptr(bits), _ptr(out), self.threads))
         return out
+
+    def label(self, llr: np.ndarray, sent: np.ndarray, max_flips: int = 8) -> dict:
+        """Decoder.label on the host (pscl_label_cpu), same keys; entries in frame order."""
+        llr = np.ascontiguousarray(llr, dtype=np.float64)
+        if llr.ndim == 1:
+            llr = llr[None, :]
+        B, K = llr.shape[0], self.K
+        if llr.shape[1] != self.N:
+            raise ValueError("Channel LLR length must be a power of two")
+        one = np.asarray(sent).ndim == 1
+        s = _sent_bits(sent, B, K)
+        frame, abs_l0 = np.zeros(B, np.int64), np.zeros((B, K), np.float32)
+        flip, rank = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        counts = np.zeros(PSCL_NLABEL, np.int64)
+        rc = lib().pscl_label_cpu(self.N, self.info_set.ctypes.data_as(C.POINTER(_i32)), K, self.L, self.crc_poly, _ptr(llr),
+                                  B, _ptr(s), 0 if one else K, int(max_flips), _ptr(frame), _ptr(abs_l0), _ptr(flip),
+                                  _ptr(rank), _ptr(counts), self.threads)
+        if rc == PSCL_EINVAL:
+            raise ValueError("invalid code, CRC (one is required), max_flips (1..32) or shapes for pscl_label_cpu")
+        check(rc)
+        A = int(counts[LBL_ENTRIES])
+        return {"frame": frame[:A].copy(), "abs_l0": abs_l0[:A].copy(), "flip": flip[:A].copy(), "rank": rank[:A].copy(),
+                "counts": counts}
 
     def sync(self) -> None:
         pass

@@ -25,9 +25,10 @@ ARCH = os.environ.get("PSCL_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 HIP_SOURCES = ["scl_kernels.hip", "scl128.hip", "scl128_spec.hip", "scl128_lane.hip", "scl128_lane_rl.hip", "sc128_lane.hip",
-               "scl128_lane_f32.hip", "scl128_lane_rl_f32.hip", "scl128_lane_fs_f32.hip", "sc128_lane_f32.hip", "scl128_spec_f32.hip", "scl128_spec_fs_f32.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "dlscl_f32.hip", "replay_long.hip", "encode.hip", "derate.hip", "capi.cpp",
+               "scl128_lane_f32.hip", "scl128_lane_rl_f32.hip", "scl128_lane_fs_f32.hip", "sc128_lane_f32.hip", "scl128_spec_f32.hip", "scl128_spec_fs_f32.hip", "sc_lane.hip", "scl_lane_long.hip", "scl_long.hip", "dlscl.hip", "dlscl_f32.hip", "replay_long.hip", "encode.hip", "derate.hip", "label.hip", "capi.cpp",
                "scl_cpu.cpp"]
-HIP_DEPS = HIP_SOURCES + ["scl_kernels.h", "scl_device.h", "scl128_impl.h", "scl_lane.h", "glibc_softplus.h", "exp_table.inc"]
+HIP_DEPS = HIP_SOURCES + ["scl_kernels.h", "scl_device.h", "scl128_impl.h", "scl_lane.h", "glibc_softplus.h", "exp_table.inc",
+                          "label_rank.h"]
 # scl128_spec.hip is compiled once per (information-set code, list size): 8 objects
 SPEC_UNITS = [(c, l) for c in (1, 2) for l in (1, 2, 4, 8)]
 # scl128_spec_f32.hip (the exact re-decode over float32 rows) and scl128_spec_fs_f32.hip (the exact

@@ -237,6 +237,12 @@ enum Slot : int {
     // the host forms' device counters (pscl_simulate, pscl_simulate_adaptive, pscl_simulate_adaptive_dl): the
     // call joins the pipelined work and waits on the host before it returns
     kSimCounters, kSimAdCounters, kSimAdDlCounters,
+    // pscl_label_device: the baseline's best words and flags, the compaction's count and frame list, the
+    // replayed L0 and the flip order by entry, the rounds' dense state (entry ids and LLR rows ping-ponged,
+    // force words, result words and flags) and their counts.  Main only, in stream order; sized after the
+    // call's host wait, when the stream is idle
+    kLblBest, kLblFlags, kLblCount, kLblAct, kLblL0, kLblOrder, kLblEnt0, kLblEnt1, kLblRow0, kLblRow1, kLblForce,
+    kLblOb, kLblOf, kLblCnt,
     kSlotCount
 };
 static_assert(kChainFields == 14 && kLongFields == 10, "a state buffer was added: size it in its table");
@@ -306,6 +312,7 @@ struct pscl_handle {
     hipEvent_t ev_base[kDlPar] = {}, ev_retry[kDlPar] = {}, ev_join[kChainSets] = {};
     int32_t* h_count = nullptr;          // pinned: failing-frame counts of the chunk parities
     int32_t* h_adapt = nullptr;          // pinned: escalated-frame count of pscl_adaptive_device
+    int32_t* h_label = nullptr;          // pinned: entry count of pscl_label_device
     double* d_beta = nullptr;         // [K][K] DL-SCL flip metric (null = |L0|)
     float* d_beta32g[2] = {nullptr, nullptr};  // K = 64: fp32 beta, [K][G][K / G] for G = 8, 4 (fused post)
     std::vector<float> beta32g_host;
@@ -2419,6 +2426,7 @@ int pscl_destroy(pscl_handle* h) {
     if (h->d_crctab) hipFree(h->d_crctab);
     if (h->h_count) hipHostFree(h->h_count);
     if (h->h_adapt) hipHostFree(h->h_adapt);
+    if (h->h_label) hipHostFree(h->h_label);
     auto drop = [](hipEvent_t e) {
         if (e) hipEventDestroy(e);
     };
@@ -2592,6 +2600,156 @@ int pscl_path_llrs_device(pscl_handle* h, const double* d_llr, int64_t B, const 
 
 int pscl_path_llrs_device_f32(pscl_handle* h, const float* d_llr, int64_t B, const uint64_t* d_bits, double* d_out) {
     return path_llrs_impl(h, d_llr, true, B, d_bits, d_out);
+}
+
+// Flip labels of a device batch (include/polar_scl.h): the baseline decode and the compaction of the
+// frames that fail the CRC, the call's one host wait for their count A, then -- all enqueued on the
+// handle's stream -- the replay of the baseline best paths (L0 by entry), the ranking (label.hip), and
+// T rounds of {forced-bit decode of the round's dense list, step}.  A round's decode reads its live
+// count on the device (d_count), its LLR rows by indirection (fidx) and one force block per frame, the
+// form the long codes' DL-SCL chain drives (dl_retry_long); every code length takes it, and every
+// round decodes from phase 0 on the exact forced-bit instance.
+int pscl_label_device(pscl_handle* h, const double* d_llr, int64_t B, const uint64_t* d_sent, int64_t sent_stride,
+                      int max_flips, int64_t cap, int64_t* d_frame, float* d_abs_l0, int32_t* d_flip, int32_t* d_rank,
+                      int64_t* d_counts, int64_t* n_entries) {
+    if (!h) return fail(PSCL_EINVAL, "NULL handle");
+    if (n_entries) *n_entries = 0;
+    if (!h->crc_poly) return fail(PSCL_EINVAL, "labelling needs a CRC (without one every baseline passes)");
+    if (max_flips < 1 || max_flips > 32) return fail(PSCL_EINVAL, "max_flips must be 1..32 (got %d)", max_flips);
+    if (B < 0) return fail(PSCL_EINVAL, "B must be >= 0");
+    if (cap < 0) return fail(PSCL_EINVAL, "cap must be >= 0");
+    if (sent_stride != 0 && sent_stride != h->W)
+        return fail(PSCL_EINVAL, "sent_stride must be 0 (one message) or W = %d (one per frame)", h->W);
+    if (B > 0 && (!d_llr || !d_sent || !d_counts || !n_entries))
+        return fail(PSCL_EINVAL, "d_llr, d_sent, d_counts and n_entries are required");
+    if (B > 0 && cap > 0 && (!d_frame || !d_abs_l0 || !d_flip))
+        return fail(PSCL_EINVAL, "d_frame, d_abs_l0 and d_flip are required");
+    if (B > INT32_MAX) return fail(PSCL_EUNSUP, "B exceeds 2^31-1");
+    int rc = enter(h);  // (pending pipelined work first; the call runs stream-ordered)
+    if (rc) return rc;
+    hipStream_t s = h->stream;
+    if (B == 0) {
+        if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, PSCL_NLABEL * 8, s));
+        return PSCL_OK;
+    }
+    const int K = h->K, W = h->W, T = max_flips < K ? max_flips : K;
+    // the baseline: the handle's plain list decode of all B frames into scratch
+    uint64_t* d_base;
+    uint8_t* d_bflags;
+    int32_t* d_cnt;
+    int64_t* d_act;
+    if ((rc = ensure_as(h, kLblBest, (size_t)B * W * 8, d_base)) || (rc = ensure_as(h, kLblFlags, (size_t)B, d_bflags)) ||
+        (rc = ensure_as(h, kLblCount, 4, d_cnt)) || (rc = ensure_as(h, kLblAct, (size_t)B * 8, d_act)))
+        return rc;
+    if (!h->h_label) HIP_TRY(hipHostMalloc((void**)&h->h_label, 4, hipHostMallocDefault));
+    pscl_decode_params P;
+    fill_decode_params(h, P, 0);
+    P.llr = d_llr;
+    P.B = B;
+    P.best = d_base;
+    P.flags = d_bflags;
+    if (pscl_decode_wpg(P) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
+    if ((rc = launch_decode(h, P, 0))) return rc;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 4, s));
+    LAUNCH_TRY("dl_compact", pscl_launch_dl_compact(d_bflags, B, 0, d_act, nullptr, d_cnt, s));
+    HIP_TRY(hipMemcpyAsync(h->h_label, d_cnt, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the call's one host wait
+    const int64_t A = *h->h_label;
+    if (A < 0 || A > B) return fail(PSCL_EDEVICE, "entry count %lld out of range", (long long)A);
+    *n_entries = A;
+    if (A > cap)
+        return fail(PSCL_EINVAL, "%lld entries exceed cap = %lld: allocate again and repeat", (long long)A, (long long)cap);
+    HIP_TRY(hipMemsetAsync(d_counts, 0, PSCL_NLABEL * 8, s));
+    if (A == 0) return PSCL_OK;  // (every frame passed: no round is launched)
+    double* d_l0;
+    int32_t *d_order, *d_ent[2], *d_rcnt;
+    int64_t* d_row[2];
+    uint64_t *d_force, *d_ob;
+    uint8_t* d_of;
+    const size_t a = (size_t)A;
+    if ((rc = ensure_as(h, kLblL0, a * K * 8, d_l0)) || (rc = ensure_as(h, kLblOrder, a * T * 4, d_order)) ||
+        (rc = ensure_as(h, kLblEnt0, a * 4, d_ent[0])) || (rc = ensure_as(h, kLblEnt1, a * 4, d_ent[1])) ||
+        (rc = ensure_as(h, kLblRow0, a * 8, d_row[0])) || (rc = ensure_as(h, kLblRow1, a * 8, d_row[1])) ||
+        (rc = ensure_as(h, kLblForce, a * 2 * W * 8, d_force)) || (rc = ensure_as(h, kLblOb, a * W * 8, d_ob)) ||
+        (rc = ensure_as(h, kLblOf, a, d_of)) || (rc = ensure_as(h, kLblCnt, (size_t)(T + 1) * 4, d_rcnt)))
+        return rc;
+    // L0 of the baseline best paths, by entry (pscl_path_llrs_device's kernels over the entry list)
+    pscl_replay_params Rp;
+    memset(&Rp, 0, sizeof(Rp));
+    Rp.llr = d_llr;
+    Rp.N = h->N;
+    Rp.n = h->n;
+    Rp.K = K;
+    Rp.W = W;
+    Rp.rm_E = h->rm_E;
+    Rp.rm_src = h->d_rm_src;
+    Rp.info_mask[0] = h->info_mask[0];
+    Rp.info_mask[1] = h->info_mask[1];
+    Rp.count = d_cnt;
+    Rp.act = d_act;
+    Rp.bits = d_base;
+    Rp.bits_by_row = 1;
+    Rp.out = d_l0;
+    const bool lng = h->N > PSCL_FAST_N;
+    if (lng) {
+        h->n_replay_launches++;
+        h->n_replay_rows += A;
+    }
+    LAUNCH_TRY("replay", lng ? pscl_launch_replay_long(Rp, A, h->d_info_words, nullptr, s) : pscl_launch_replay(Rp, A, s));
+    pscl_label_rank_params R;
+    memset(&R, 0, sizeof(R));
+    R.l0 = d_l0;
+    R.A = A;
+    R.K = K;
+    R.T = T;
+    R.abs_l0 = d_abs_l0;
+    R.order = d_order;
+    LAUNCH_TRY("label_rank", pscl_launch_label_rank(R, s));
+    HIP_TRY(hipMemsetAsync(d_rcnt, 0, (size_t)(T + 1) * 4, s));
+    pscl_label_step_params S;
+    memset(&S, 0, sizeof(S));
+    S.K = K;
+    S.W = W;
+    S.T = T;
+    S.A = A;
+    S.ob = d_ob;
+    S.of = d_of;
+    S.act = d_act;
+    S.base = d_base;
+    S.sent = d_sent;
+    S.sent_stride = sent_stride;
+    S.order = d_order;
+    S.force_out = d_force;
+    S.frame = d_frame;
+    S.flip = d_flip;
+    S.rank = d_rank;
+    S.counts = d_counts;
+    S.t = -1;  // the first launch builds round 0
+    S.out_count = d_rcnt;
+    S.ent_out = d_ent[0];
+    S.row_out = d_row[0];
+    LAUNCH_TRY("label_step", pscl_launch_label_step(S, s));
+    pscl_decode_params H;
+    fill_decode_params(h, H, 0);
+    H.llr = d_llr;
+    H.B = A;
+    H.force = d_force;
+    H.best = d_ob;
+    H.flags = d_of;
+    if (pscl_decode_wpg(H) < 1) return fail(PSCL_EUNSUP, "LDS budget exceeded (L=%d, K=%d)", h->L, h->K);
+    for (int t = 0; t < T; ++t) {  // no host round trips: the live counts stay on the device
+        H.fidx = d_row[t & 1];
+        H.d_count = d_rcnt + t;
+        if ((rc = launch_decode(h, H, 0))) return rc;
+        S.t = t;
+        S.in_count = d_rcnt + t;
+        S.ent_in = d_ent[t & 1];
+        S.out_count = t + 1 < T ? d_rcnt + t + 1 : nullptr;
+        S.ent_out = d_ent[(t + 1) & 1];
+        S.row_out = d_row[(t + 1) & 1];
+        LAUNCH_TRY("label_step", pscl_launch_label_step(S, s));
+    }
+    return PSCL_OK;
 }
 
 int pscl_set_beta(pscl_handle* h, const double* beta) {

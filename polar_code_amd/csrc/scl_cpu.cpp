@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "glibc_softplus.h"
+#include "label_rank.h"
 #include "polar_scl.h"
 
 namespace {
@@ -250,6 +251,99 @@ extern "C" int pscl_path_llrs_cpu(int N, const int32_t* info_set, int K, const d
         for (int t = 0; t < T; ++t) pool.emplace_back(work, t);
         for (auto& th : pool) th.join();
     }
+    return PSCL_OK;
+}
+
+// pscl_label_device's contract on the host (make_dataset.py:52-91 per frame): the baseline decode; for
+// a frame that fails the CRC the replay of its best path, the flip order (label_rank.h, shared with the
+// device kernel) and up to T forced decodes on the BASELINE's prefix, the first that passes the CRC and
+// equals the sent message giving the label.  Each thread keeps the entries of its contiguous frame
+// range; written out in thread order they are in frame order.
+extern "C" int pscl_label_cpu(int N, const int32_t* info_set, int K, int L, uint64_t crc_poly, const double* llr, int64_t B,
+                              const int8_t* sent, int64_t sent_stride, int max_flips, int64_t* frame, float* abs_l0,
+                              int32_t* flip, int32_t* rank, int64_t* counts, int threads) {
+    if (N < 2 || N > PSCL_MAX_N || (N & (N - 1))) return PSCL_EINVAL;
+    if (L < 1 || L > 255 || K < 1 || K > N || B < 0 || !info_set) return PSCL_EINVAL;
+    for (int i = 0; i < K; ++i)
+        if (info_set[i] < 0 || info_set[i] >= N || (i && info_set[i] <= info_set[i - 1])) return PSCL_EINVAL;
+    if (!crc_poly) return PSCL_EINVAL;  // (without a CRC every baseline passes)
+    const int deg = 63 - __builtin_clzll(crc_poly);
+    if (deg <= 0 || K <= deg) return PSCL_EINVAL;
+    if (max_flips < 1 || max_flips > PSCL_LABEL_MAX_FLIPS) return PSCL_EINVAL;
+    if (sent_stride != 0 && sent_stride != K) return PSCL_EINVAL;
+    if (B > 0 && (!llr || !sent || !frame || !abs_l0 || !flip || !counts)) return PSCL_EINVAL;
+    if (counts)
+        for (int i = 0; i < PSCL_NLABEL; ++i) counts[i] = 0;
+    if (B == 0) return PSCL_OK;
+    const int T = max_flips < K ? max_flips : K;
+    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if ((int64_t)nt > B) nt = (int)B;
+    struct Part {
+        std::vector<int64_t> frame;
+        std::vector<float> abs_l0;
+        std::vector<int32_t> flip, rank;
+        int64_t decodes = 0;
+    };
+    std::vector<Part> parts((size_t)nt);
+    auto work = [&](int t) {
+        Part& out = parts[(size_t)t];
+        CpuScl dec(N, info_set, K, L, crc_poly);
+        std::vector<double> tmp((size_t)N), leaf((size_t)N), l0((size_t)K);
+        std::vector<uint8_t> u((size_t)N), x((size_t)N);
+        std::vector<int8_t> base((size_t)K), cand((size_t)K), forced((size_t)K);
+        std::vector<float> a((size_t)K);
+        int32_t order[PSCL_LABEL_MAX_FLIPS];
+        const int64_t b0 = B * t / nt, b1 = B * (t + 1) / nt;
+        for (int64_t b = b0; b < b1; ++b) {
+            const double* row = llr + b * N;
+            uint8_t ok = 0;
+            dec.decode(row, nullptr, nullptr, base.data(), &ok, nullptr, nullptr, nullptr, nullptr);
+            if (ok) continue;
+            std::fill(u.begin(), u.end(), (uint8_t)0);
+            for (int i = 0; i < K; ++i) u[(size_t)info_set[i]] = (uint8_t)base[(size_t)i];
+            replay_segment(row, N, 0, u.data(), tmp.data(), leaf.data(), x.data());
+            for (int i = 0; i < K; ++i) l0[(size_t)i] = leaf[(size_t)info_set[i]];
+            pscl_label_rank_host(l0.data(), K, T, a.data(), order);
+            const int8_t* want = sent + b * sent_stride;
+            int32_t lab = -1, rk = -1;
+            for (int r = 0; r < T && lab < 0; ++r) {
+                const int idx = order[r];
+                for (int i = 0; i < K; ++i) forced[(size_t)i] = i < idx ? base[(size_t)i] : (int8_t)-1;
+                forced[(size_t)idx] = (int8_t)(1 - base[(size_t)idx]);
+                dec.decode(row, forced.data(), nullptr, cand.data(), &ok, nullptr, nullptr, nullptr, nullptr);
+                out.decodes++;
+                if (ok && memcmp(cand.data(), want, (size_t)K) == 0) {
+                    lab = idx;
+                    rk = r;
+                }
+            }
+            out.frame.push_back(b);
+            out.abs_l0.insert(out.abs_l0.end(), a.begin(), a.end());
+            out.flip.push_back(lab);
+            out.rank.push_back(rk);
+        }
+    };
+    if (nt == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < nt; ++t) pool.emplace_back(work, t);
+        for (auto& th : pool) th.join();
+    }
+    int64_t e = 0;
+    for (const Part& p : parts) {
+        const size_t n = p.frame.size();
+        for (size_t i = 0; i < n; ++i, ++e) {
+            frame[e] = p.frame[i];
+            memcpy(abs_l0 + e * K, p.abs_l0.data() + i * (size_t)K, (size_t)K * sizeof(float));
+            flip[e] = p.flip[i];
+            if (rank) rank[e] = p.rank[i];
+            counts[p.flip[i] >= 0 ? PSCL_LBL_LABELLED : PSCL_LBL_UNREPAIRED]++;
+        }
+        counts[PSCL_LBL_DECODES] += p.decodes;
+    }
+    counts[PSCL_LBL_ENTRIES] = e;
     return PSCL_OK;
 }
 

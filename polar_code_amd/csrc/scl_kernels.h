@@ -487,4 +487,44 @@ hipError_t pscl_launch_dl_post_long(const pscl_post_long_params& Q, hipStream_t 
 hipError_t pscl_launch_dl_count(const uint64_t* best, const uint8_t* flags, const uint64_t* ref, int64_t B, int W,
                                 int k_payload, int64_t* counters, hipStream_t s);
 
+// Flip labels (label.hip; pscl_label_device): entry e = one frame whose baseline fails the CRC.
+// Ranking: abs_l0[e][k] = |(float)l0[e][k]| and order[e][t], t < T, the information indices of the T
+// smallest values, ascending, ties to the lower index (label_rank.h).
+struct pscl_label_rank_params {
+    const double* l0;            // [A][K] decision LLRs of the baseline best paths, by entry
+    int64_t A;
+    int K, T;
+    float* abs_l0;               // [A][K]
+    int32_t* order;              // [A][T]
+};
+hipError_t pscl_launch_label_rank(const pscl_label_rank_params& R, hipStream_t s);
+// The step between rounds.  A round's decode is dense: its frame i reads LLR row row[i] and force[i]
+// and writes ob[i] / of[i]; ent[i] is the entry behind it.  Launch t (t = 0 .. T - 1, after round t's
+// decode) labels the entries whose result passes the CRC and equals the sent words (flip = order[e][t],
+// rank = t), gives the rest -1 after the last round, and otherwise appends them to round t + 1's dense
+// state with the force words of order[e][t + 1] on the BASELINE words.  The first launch (t = -1)
+// builds round 0 from all A entries and writes frame[e] and counts[PSCL_LBL_ENTRIES].
+struct pscl_label_step_params {
+    int K, W, T, t;
+    int64_t A;
+    const int32_t* in_count;     // [1] frames of round t's decode (t >= 0)
+    const int32_t* ent_in;       // [A] (t >= 0)
+    const uint64_t* ob;          // [A][W] round t's best words (t >= 0)
+    const uint8_t* of;           // [A] its flags
+    const int64_t* act;          // [A] frame of entry e (the compaction's list)
+    const uint64_t* base;        // [B][W] baseline best words, by frame
+    const uint64_t* sent;        // sent words: frame f's at sent + f * sent_stride
+    int64_t sent_stride;
+    const int32_t* order;        // [A][T]
+    int32_t* out_count;          // [1] frames of round t + 1 (zeroed before the launch; null after the last round)
+    int32_t* ent_out;            // [A]
+    int64_t* row_out;            // [A]
+    uint64_t* force_out;         // [A][2][W]
+    int64_t* frame;              // [cap] out (t = -1)
+    int32_t* flip;               // [cap] out
+    int32_t* rank;               // [cap] out, or null
+    int64_t* counts;             // [PSCL_NLABEL] (zeroed before the first launch)
+};
+hipError_t pscl_launch_label_step(const pscl_label_step_params& S, hipStream_t s);
+
 #endif

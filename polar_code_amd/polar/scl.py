@@ -393,6 +393,52 @@ class SCLDecoder:
             self._dec.join()  # (the widened temporary: see decode_tensor)
         return out
 
+    def label(self, llr: np.ndarray, sent: np.ndarray, max_flips: int = 8) -> dict:
+        """Flip labels for beta training (pscl_label_device, or pscl_label_cpu on a device="cpu"
+        decoder): llr [B, N] float64, sent [K] or [B, K] 0/1 -> dict(frame, abs_l0, flip, rank,
+        counts), one row per frame whose baseline fails the CRC, sorted by frame."""
+        return self._dec.label(llr, sent, max_flips)
+
+    def label_tensor(self, llr, sent_words, max_flips: int = 8):
+        """label on the caller's current torch stream: llr a contiguous float64 [B, N] (or [B, E])
+        tensor on this GPU, sent_words a contiguous int64 [W] (one message for all frames) or [B, W]
+        tensor of the sent message words (transmit_tensor's msg).  Returns dict(frame [A] int64,
+        abs_l0 [A, K] float32, flip [A] int32, rank [A] int32, counts int64[4]) of tensors, entries
+        sorted by frame.  The call waits once on the host, for the entry count."""
+        import torch
+
+        if self.device == "cpu":
+            raise ValueError("the tensor methods need a GPU decoder")
+        dec = self._dec
+        if self._f32_rows(llr, dec.E or self.N):
+            raise ValueError("label_tensor takes float64 rows")
+        B, W, K = llr.shape[0], dec.W, self.K
+        if (not isinstance(sent_words, torch.Tensor) or sent_words.dtype != torch.int64 or not sent_words.is_contiguous()
+                or tuple(sent_words.shape) not in ((W,), (B, W))):
+            raise ValueError(f"sent_words must be a contiguous int64 [{W}] or [B, {W}] tensor")
+        if llr.device.type != "cuda" or llr.device.index != self.device or sent_words.device != llr.device:
+            raise ValueError(f"llr and sent_words must be on GPU {self.device}")
+        stride = 0 if sent_words.dim() == 1 else W
+        counts = torch.zeros((_native.PSCL_NLABEL,), dtype=torch.int64, device=llr.device)
+        dec.set_stream(torch.cuda.current_stream(llr.device).cuda_stream)
+        cap = _native.label_capacity(B, K)
+        for _ in range(2):
+            frame = torch.empty((cap,), dtype=torch.int64, device=llr.device)
+            abs_l0 = torch.empty((cap, K), dtype=torch.float32, device=llr.device)
+            flip = torch.empty((cap,), dtype=torch.int32, device=llr.device)
+            rank = torch.empty((cap,), dtype=torch.int32, device=llr.device)
+            try:
+                A = dec.label_device(llr.data_ptr(), B, sent_words.data_ptr(), stride, max_flips, cap,
+                                     d_frame=frame.data_ptr(), d_abs_l0=abs_l0.data_ptr(), d_flip=flip.data_ptr(),
+                                     d_rank=rank.data_ptr(), d_counts=counts.data_ptr())
+                break
+            except _native.LabelCapacity as e:
+                if cap >= e.entries:
+                    raise
+                cap = e.entries
+        o = torch.argsort(frame[:A], stable=True)
+        return {"frame": frame[:A][o], "abs_l0": abs_l0[:A][o], "flip": flip[:A][o], "rank": rank[:A][o], "counts": counts}
+
     # ---- caller payloads: payload -> CRC -> codeword (-> symbols or AWGN LLR rows) on the device
     def encode(self, payload_bits: np.ndarray, device=None) -> dict:
         """payload_bits [B, k_payload] 0/1 (k_payload = K - CRC degree) -> dict(msg [B, K] int8 =

@@ -19,6 +19,13 @@ Same CLI, same shard (``{out}_part0.npz``: ``abs_l0`` float32[S, K], ``flip_idx`
 ``--rng philox`` generates the frames on the GPU (counter-based, independent of batching)
 and maps them to the all-zero codeword by the channel's symmetry (LLR sign flip where the
 sent bit is 1: same noise law), for datasets far larger than the NumPy stream makes sense for.
+
+``--label native`` (default ``host``, the loop above) labels a batch in one native call
+(``pscl_label_device``; ``pscl_label_cpu`` with ``--device cpu``): baseline, replay, order, forced
+retries and labels without a host trip per round, same shards.  With ``--rng philox`` the frames
+stay on the device and are labelled by their own messages (no symmetry mapping; only the failing
+frames' ``|L0|`` rows and labels are downloaded).  Equal ``|L0|`` values resolve to the lower index
+there, where ``np.argsort``'s order on ties depends on the NumPy build.
 """
 from __future__ import annotations
 
@@ -60,7 +67,9 @@ def _force_prefix_flip(bits: np.ndarray, idx: np.ndarray) -> np.ndarray:
 
 
 def label_batch(llr: np.ndarray, info_set, M: int, crc: str, sent: np.ndarray, device=0):
-    """Samples of one batch, in frame order: (abs_l0 float32 [S, K], labels int32 [S], failures)."""
+    """Samples of one batch, in frame order: (abs_l0 float32 [S, K], labels int32 [S], failures).
+    sent: the one sent message [K], or each frame's own [B, K]."""
+    sent = np.asarray(sent)
     on = {} if device == 0 else {"device": device}  # (the default device: the helpers' own)
     bits, ok = decode_batch(llr, info_set, M, crc, **on)
     fail = np.flatnonzero(~ok)
@@ -78,10 +87,54 @@ def label_batch(llr: np.ndarray, info_set, M: int, crc: str, sent: np.ndarray, d
             break
         idx = order[todo, t]
         cand, cpass = decode_batch(llr[fail[todo]], info_set, M, crc, _force_prefix_flip(base[todo], idx), **on)
-        hit = cpass & np.all(cand == sent[None, :], axis=1)
+        want = sent[None, :] if sent.ndim == 1 else sent[fail[todo]]
+        hit = cpass & np.all(cand == want, axis=1)
         label[todo[hit]] = idx[hit]
     keep = label >= 0
     return abs_l0[keep], label[keep], int(np.count_nonzero(~keep))
+
+
+def label_batch_native(llr: np.ndarray, info_set, M: int, crc: str, sent: np.ndarray, device=0):
+    """label_batch as one native call (--label native): pscl_label_device on GPU `device`, or
+    pscl_label_cpu with device "cpu".  Same return value; on ties of |L0| the order is the engine's
+    (the lower index first), where np.argsort's depends on the NumPy build."""
+    out = _native.get_decoder(llr.shape[1], info_set, M, crc, device).label(llr, sent, max_flips=8)
+    keep = out["flip"] >= 0
+    return out["abs_l0"][keep], out["flip"][keep], int(out["counts"][_native.LBL_UNREPAIRED])
+
+
+def _philox_label_native(seed: int, snr_db: float, frame0: int, n: int, info_set, M: int, crc: str, kp: int, device=0):
+    """n frames from the device TX chain, labelled where they lie: channel_device, then label_device
+    on its rows with the frames' own message words as the sent words -- no symmetry mapping, and only
+    the entries' rows (the failing frames' |L0| and labels) are downloaded.  Returns label_batch's tuple."""
+    cfg = config.get_config()
+    dec = _native.get_decoder(cfg.N, info_set, M, crc, device)
+    W, K = dec.W, dec.K
+    with _native.DeviceArena(dec) as mem:
+        d_llr = mem.alloc(n * cfg.N * 8)
+        d_msg = mem.alloc(n * W * 8)
+        d_counts = mem.alloc(_native.PSCL_NLABEL * 8)
+        dec.channel_device(seed, 0x7FFF0000 + int(round(snr_db * 10)), snr_db, cfg.K / cfg.N, kp, frame0, n, d_llr, d_msg)
+        cap = _native.label_capacity(n, K)
+        for _ in range(2):
+            d_frame, d_abs, d_flip = mem.alloc(cap * 8), mem.alloc(cap * K * 4), mem.alloc(cap * 4)
+            try:
+                A = dec.label_device(d_llr, n, d_msg, W, 8, cap, d_frame=d_frame, d_abs_l0=d_abs, d_flip=d_flip,
+                                     d_counts=d_counts)
+                break
+            except _native.LabelCapacity as e:
+                if cap >= e.entries:
+                    raise
+                cap = e.entries
+        dec.sync()
+        counts = mem.download(d_counts, _native.PSCL_NLABEL * 8, np.int64)
+        frame = mem.download(d_frame, cap * 8, np.int64)[:A]
+        abs_l0 = mem.download(d_abs, cap * K * 4, np.float32)[:A * K].reshape(A, K)
+        flip = mem.download(d_flip, cap * 4, np.int32)[:A]
+    o = np.argsort(frame, kind="stable")
+    abs_l0, flip = abs_l0[o], flip[o]
+    keep = flip >= 0
+    return abs_l0[keep], flip[keep], int(counts[_native.LBL_UNREPAIRED])
 
 
 def _philox_frames(seed: int, snr_db: float, frame0: int, n: int, info_set, M: int, crc: str, kp: int):
@@ -116,15 +169,25 @@ def generate_samples(args: argparse.Namespace) -> Path:
     xs: List[np.ndarray] = []
     ys: List[np.ndarray] = []
     failures = 0
+    dev = getattr(args, "device", "0")
+    dev = "cpu" if dev == "cpu" else int(dev)
+    native = getattr(args, "label", "host") == "native"
+    if native and args.rng == "philox" and dev == "cpu":
+        raise ValueError("--rng philox generates frames on the GPU: use a GPU --device")
     for b0 in range(0, args.frames, args.batch):
         n = min(args.batch, args.frames - b0)
+        if native and args.rng == "philox":  # generated and labelled on the device, by the frames' own messages
+            a, lab, nf = _philox_label_native(args.seed, args.snr_db, b0, n, info_set, args.M, cfg.crc_poly, payload_bits, dev)
+            xs.append(a)
+            ys.append(lab)
+            failures += nf
+            continue
         if args.rng == "replay":
             noise = rng.normal(0.0, sigma, size=(n, cfg.N))  # = n successive size-N draws
             llr = 2.0 * (symbols[None, :] + noise) / noise_var
         else:
             llr = _philox_frames(args.seed, args.snr_db, b0, n, info_set, args.M, cfg.crc_poly, payload_bits)
-        dev = getattr(args, "device", "0")
-        a, lab, nf = label_batch(llr, info_set, args.M, cfg.crc_poly, sent, "cpu" if dev == "cpu" else int(dev))
+        a, lab, nf = (label_batch_native if native else label_batch)(llr, info_set, args.M, cfg.crc_poly, sent, dev)
         xs.append(a)
         ys.append(lab)
         failures += nf
@@ -156,6 +219,9 @@ def build_argparser() -> argparse.ArgumentParser:
                    help="replay: the reference's NumPy stream (identical samples); philox: GPU-generated frames")
     p.add_argument("--batch", type=int, default=1 << 16, help="frames per GPU batch")
     p.add_argument("--device", type=str, default="0", help="GPU index, or cpu: the host decoder and its replay")
+    p.add_argument("--label", choices=["host", "native"], default="host",
+                   help="host: the NumPy loop around batched decodes; native: one labelling call per batch "
+                        "(pscl_label_device, or pscl_label_cpu with --device cpu)")
     return p
 
 
